@@ -22,7 +22,11 @@ v_mfma_f32_32x32x2_f32 kernels; the JSON line carries those figures too (`alt_ma
 fp16 operands, fp32 accumulation and BatchNorm statistics): the reduced-precision arithmetic of BASELINE configs[4]
 (`--size 512 --iters 10 --ways 2 --batch 4 --conv-math f16`), reported with dtype "f16", never the headline.
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live: every C-ABI call of one extra
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps and prints the headline (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, the per-step spread `step_ms`).
+`--dump-outputs DIR` also writes what the last timed step handed its caller (loss, gradients) as .npy files (`dump_outputs`).
+Everything else below (roofline, alt_math, mask_tile_skip, graph_replay, eval, conv_math_error_vs_fp64, cpu_baseline,
+other_configs, the other issue mode of an N > 1 run) runs only with `--full`.  `roofline` is measured live: every C-ABI call of one extra
 step is bracketed by HIP events on the launch stream; the dominant kernel is the implicit-GEMM
 convolution (rpnet_conv_fwd: forward + dgrad launches).  The timed steps run with
 the weight gradients on a second HIP stream (overlap on); the extra profiled step serialises the
@@ -124,6 +128,32 @@ def step(net, bucket, inp, scaler, exposed=None):
     # (detached: a loss tensor that outlives the step keeps the step's autograd nodes — among them every parameter's AccumulateGrad
     # node, stamped with the stream it first ran on — alive into a later leg that runs the same layers on another stream layout)
     return loss.detach()
+
+
+DUMP_GRAD_SAMPLE = 1 << 23     # float32 gradient elements --dump-outputs writes at most (32 MiB; the whole dump stays below 64 MB)
+
+
+def dump_outputs(path, loss, bucket):
+    """--dump-outputs: what the timed step hands its caller, from the last timed step — the loss (`loss.npy`, float64) and the
+    gradients every parameter's .grad views in the flat bucket.  The bucket (139 MB at the headline shape) is larger than the
+    dump's budget: `grad_sample.npy` holds the elements at a fixed, seeded set of sorted indices (the same set for every bucket of
+    the same size: numpy default_rng(0)), `grad_norms.npy` the L2 norm of every parameter's gradient (float64, bucket order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = bucket.flat
+    n = flat.numel()
+    if n > DUMP_GRAD_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_GRAD_SAMPLE, replace=False))
+        sample = flat[torch.from_numpy(idx).to(flat.device)]
+    else:
+        sample = flat
+    bounds = [0]
+    for _, p in bucket.params:
+        bounds.append(bounds[-1] + p.numel())
+    norms = torch.stack([flat[a:b].double().norm() for a, b in zip(bounds[:-1], bounds[1:])])
+    np.save(os.path.join(path, "loss.npy"), loss.detach().double().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "grad_sample.npy"), sample.float().cpu().numpy())
+    np.save(os.path.join(path, "grad_norms.npy"), norms.cpu().numpy())
 
 
 def mask_skip_leg(net, bucket, inp, scaler, batch, fence, RF, dense_value):
@@ -601,10 +631,11 @@ def cpu_baseline(cfg, size, T, seconds_budget=18.0, net=None, bucket=None, dev=N
 DDP_GRAPH = os.environ.get("RPNET_BENCH_DDP_GRAPH", "1") == "1"
 
 
-def measure(w, world, rank, dev, cfg, steps, warmup, RF, ddp=None, init_group=None):
+def measure(w, world, rank, dev, cfg, steps, warmup, RF, ddp=None, init_group=None, full=True, dump_dir=None):
     """Times `steps` steps of workload w = dict(ways, shots, size, iters, batch, conv_math) after `warmup` untimed ones
-    (barrier + synchronize on both sides, MAX over ranks), then one extra profiled step (HIP events per C-ABI call,
-    streams serialised).  -> dict with value, ms_per_step, the per-call aggregate, the arithmetic that ran, the model."""
+    (barrier + synchronize on both sides, MAX over ranks); with `full`, then one extra profiled step (HIP events per C-ABI call,
+    streams serialised) and (N > 1) the other way of issuing the step.  `dump_dir`: rank 0 writes the last timed step's
+    outputs there (dump_outputs).  -> dict with value, ms_per_step, the per-call aggregate, the arithmetic that ran, the model."""
     from rpnet_amd.parallel import FlatGradBucket, broadcast_parameters
     ddp = (world > 1) if ddp is None else ddp      # the gradient exchange runs (N > 1, or the forced one-rank RCCL group)
     cfg = dict(cfg)
@@ -690,6 +721,8 @@ def measure(w, world, rank, dev, cfg, steps, warmup, RF, ddp=None, init_group=No
         host.append(time.perf_counter() - h0)
     fence()
     el = time.perf_counter() - t0
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, loss, bucket)       # before any later step overwrites the bucket
     gts = None
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
     spread = {"min": round(step_ms[0], 3), "median": round(step_ms[len(step_ms) // 2], 3), "max": round(step_ms[-1], 3),
@@ -721,7 +754,7 @@ def measure(w, world, rank, dev, cfg, steps, warmup, RF, ddp=None, init_group=No
         # been exercised with ONE rank here (no multi-GPU lease in any round), and a crash in an informational leg would take the
         # headline line with it.  The replay form stays captured: it is the fallback the probe above switches to when any rank's
         # host cannot keep ahead of its GPU.
-        if pre_gts is None or (world > 1 and os.environ.get("RPNET_BENCH_DDP_OTHER", "0") != "1" and mode == "eager"):
+        if not full or pre_gts is None or (world > 1 and os.environ.get("RPNET_BENCH_DDP_OTHER", "0") != "1" and mode == "eager"):
             # (also: no replay form without the graph captured before the group existed — gloo plumbing runs, RPNET_BENCH_DDP_GRAPH=0)
             other = None
         else:
@@ -764,9 +797,11 @@ def measure(w, world, rank, dev, cfg, steps, warmup, RF, ddp=None, init_group=No
     # peak of torch's allocator over model, inputs, warm-up and the timed steps (the tensors an asynchronous weight gradient reads
     # are kept alive until the side streams are joined at the end of backward: this is what that costs)
     peak_gb = round(torch.cuda.max_memory_allocated(dev) / 2.0 ** 30, 2)
-    RF.reset_arith()
-    agg = profile_step(net, bucket, inp, scaler)
-    arith = RF.arith_counts()          # which arithmetic every conv / correlation launch of that step actually ran
+    agg = arith = None
+    if full:
+        RF.reset_arith()
+        agg = profile_step(net, bucket, inp, scaler)
+        arith = RF.arith_counts()          # which arithmetic every conv / correlation launch of that step actually ran
     return {"value": world * w["batch"] * steps / el, "el": el, "spread": spread, "agg": agg, "arith": arith, "math": math, "requested": requested,
             "peak_gb": peak_gb,
             "net": net, "bucket": bucket, "inp": inp, "scaler": scaler, "cfg": cfg, "dist": dist_info, "fence": fence}
@@ -917,11 +952,17 @@ def main():
     ap.add_argument("--shots", type=int, default=1, help="support shots (5 with --batch 16 = BASELINE configs[2])")
     ap.add_argument("--ways", type=int, default=1, help="ways (2 with --size 512 --iters 10 --batch 4 --conv-math f16 = "
                                                         "BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every informational leg as well: roofline (one extra profiled step), alt_math, "
+                         "mask_tile_skip, graph_replay, eval, conv_math_error_vs_fp64, cpu_baseline, other_configs, and the other "
+                         "issue mode of an N > 1 run; without it the run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and gradients to DIR/*.npy (bench.dump_outputs)")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="all CPU legs of BASELINE.md §4 (as-written and algorithmic, B=1 and B=8, and configs[0]); minutes")
+                    help="with --full: all CPU legs of BASELINE.md §4 (as-written and algorithmic, B=1 and B=8, and configs[0]); minutes")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the BASELINE configs[2] / configs[4] legs the default single-GPU command appends (`other_configs`)")
+                    help="skip the BASELINE configs[2] / configs[4] legs the --full single-GPU command appends (`other_configs`)")
     ap.add_argument("--conv-math", choices=sorted(MATH), default=None,
                     help="arithmetic of the 3x3 convolutions (default: the library's, f16x2 = fp32-equivalent fp16 split; "
                          "f16 = plain fp16 operands, configs[4] only)")
@@ -971,14 +1012,16 @@ def main():
     # library's default) leaves out work the algorithmic FLOP count of the metric contains; it gets its own leg (mask_tile_skip)
     RF._MASK_SKIP = False
     # (N > 1: measure() creates the process group itself, AFTER it has captured the replay form of the step — see DDP_GRAPH)
-    m = measure(w, world, rank, dev, cfg, args.steps, args.warmup, RF, ddp, init_group if ddp else None)
+    full = args.full      # the informational legs below run only with --full: a plain run is the headline and nothing else
+    m = measure(w, world, rank, dev, cfg, args.steps, args.warmup, RF, ddp, init_group if ddp else None, full=full,
+                dump_dir=args.dump_outputs)
     math, requested, value = m["math"], m["requested"], m["value"]
     net, bucket, inp, scaler, fence = m["net"], m["bucket"], m["inp"], m["scaler"], m["fence"]
     cfg = m["cfg"]
 
     result = None
     alt = None
-    if world == 1 and not ddp and not args.no_cpu_baseline:
+    if full and world == 1 and not ddp and not args.no_cpu_baseline:
         # the same step under the other fp32-equivalent convolution arithmetics, for reference
         alt = {}
         for other in ("f32", "f16x2", "bf16x3"):
@@ -995,10 +1038,10 @@ def main():
             alt[other] = {"value": round(args.batch * 5 / (time.perf_counter() - t1), 3), "unit": "pairs/s", "steps": 5}
         RF.set_conv_math(requested)
     skip_leg = None
-    if world == 1 and not ddp:
+    if full and world == 1 and not ddp:
         skip_leg = mask_skip_leg(net, bucket, inp, scaler, args.batch, fence, RF, value)
     graph_leg = None
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         # the same step replayed from a HIP graph (rpnet_amd.graph.GraphedTrainStep): the host then enqueues ONE launch per step
         graph_leg = graph_replay_leg(net, bucket, inp, scaler, args.batch, fence, 10)
     if rank == 0:
@@ -1011,12 +1054,13 @@ def main():
             "config": {"workload": workload_text(w, world),
                        "global_batch": world * args.batch, "parallelism": f"dp{world}", "conv_math": math,
                        "conv_math_requested": requested,
-                       "launches_by_arithmetic": m["arith"],
                        "streams": stream_layout(),
                        "grad_allreduce_mb": round(bucket.numel * 4 / 1e6, 1)},
-            "roofline": roofline_of(m, w, world),
             "peak_allocated_gb": m["peak_gb"],
         }
+        if full:
+            result["config"]["launches_by_arithmetic"] = m["arith"]
+            result["roofline"] = roofline_of(m, w, world)
         if m["dist"]:
             result["distributed"] = m["dist"]
         if graph_leg:
@@ -1025,15 +1069,15 @@ def main():
             result["mask_tile_skip"] = skip_leg
         if alt:
             result["alt_math"] = alt
-        if world == 1 and not args.no_cpu_baseline and args.ways == 1 and args.shots == 1:
+        if full and world == 1 and not args.no_cpu_baseline and args.ways == 1 and args.shots == 1:
             result["eval"] = eval_leg(net, cfg, dev, args.size, RF)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             result["conv_math_error_vs_fp64"] = {k: float(f"{v:.3g}") for k, v in conv_accuracy_probe(dev).items()}
-        if world == 1 and not args.no_cpu_baseline and args.shots == 1 and args.ways == 1:
+        if full and world == 1 and not args.no_cpu_baseline and args.shots == 1 and args.ways == 1:
             result["cpu_baseline"] = cpu_baseline(cfg, args.size, args.iters, net=net, bucket=bucket, dev=dev,
                                                   full=args.cpu_baseline_full)
             result["cpu_baseline"]["gpu_over_cpu"] = round(value / result["cpu_baseline"]["value"], 1)
-    if world == 1 and not ddp and headline and not args.no_other_configs:
+    if full and world == 1 and not ddp and headline and not args.no_other_configs:
         # the secondary BASELINE configurations that fit one GPU, timed by the same command (3 warm-up + 5 timed steps each,
         # their own roofline): configs[2] = 5-shot, batch 16; configs[4] = 2-way 512^2, T = 10, one fp16 plane, at its
         # per-GPU batch of 4 (global batch 32 across 8 GPUs)

@@ -480,6 +480,7 @@ class RP_Net(nn.Module):
         # (one way, one shot: the support tensor itself — torch.cat of a single tensor is a copy launch each)
         supp = (supp_imgs[0][0] if n_ways * n_shots == 1 else torch.cat([torch.cat(way, 0) for way in supp_imgs], 0)).float()
         qry = qry_imgs[0].float()
+        RF.hip.require_gpu(supp, qry)      # before the first launch: a kernel handed host pointers faults the device
         ns = supp.shape[0]
         # eval mode: with predicted scales (RF.pred_*: the previous call's maxima) the fp16 planes cost no extra pass, so they
         # pay from the training threshold on; RF._EVAL_PREDICT = False keeps round 2's measured scales and their higher threshold

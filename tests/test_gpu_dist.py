@@ -218,7 +218,7 @@ def test_bench_forced_rccl_group_on_one_gpu():
     env = dict(os.environ, RPNET_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RPNET_DIST_BACKEND", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "128",
-           "--iters", "2", "--no-cpu-baseline"]
+           "--iters", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -239,7 +239,7 @@ def test_bench_two_ranks_on_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--batch", "2", "--size", "128", "--iters", "2", "--no-cpu-baseline"]
+           "--warmup", "1", "--batch", "2", "--size", "128", "--iters", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -253,6 +253,36 @@ def test_bench_two_ranks_on_one_gpu():
     # eager + overlapped exchange here; the graph-replay form is measured under RCCL only (test_bench_forced_rccl_group_on_one_gpu):
     # a HIP stream capture beside gloo's helper threads crashes or hangs on this ROCm (bench.py)
     assert dinfo["issued"] == "eager" and dinfo["other_issue_mode"] is None
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain bench.py run times exactly --steps steps, prints the headline line without any --full leg, and --dump-outputs
+    writes the last timed step's loss and gradients (float32 / float64, below 64 MB) that agree with the line."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "RPNET_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "2", "--size", "128",
+           "--iters", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["steps"] == 4 and res["ms_per_step"] > 0 and res["value"] > 0 and res["unit"] == "pairs/s"
+    assert res["higher_is_better"] is True and res["dtype"] == "f32" and res["metric"].startswith("support/query pairs/sec")
+    assert abs(res["value"] - 2 * 1e3 / res["ms_per_step"]) < 0.01 * res["value"]
+    for key in ("roofline", "alt_math", "mask_tile_skip", "graph_replay", "eval", "cpu_baseline", "other_configs"):
+        assert key not in res, key
+    import numpy as np
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["grad_norms.npy", "grad_sample.npy", "loss.npy"], files
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum((out / f).stat().st_size for f in files) < 64 * 2 ** 20
+    assert arrays["loss"].shape == (1,) and np.isfinite(arrays["loss"]).all() and arrays["loss"][0] > 0
+    assert np.isfinite(arrays["grad_sample"]).all() and np.abs(arrays["grad_sample"]).max() > 0
+    assert np.isfinite(arrays["grad_norms"]).all() and (arrays["grad_norms"] > 0).any()
+    # the bucket (grad_allreduce_mb) is larger than the dump's budget: a fixed sample of 2^23 of its elements
+    assert res["config"]["grad_allreduce_mb"] * 1e6 / 4 > 1 << 23 and arrays["grad_sample"].size == 1 << 23
 
 
 def _train_worker(rank, world, port, q):

@@ -344,19 +344,44 @@ def test_dma_kernels_not_chosen_beyond_their_32_bit_range():
             assert variant(64, 512, 512, 64, 128, planes, tune) not in (11, 12, 13, 14), (planes, tune)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/test_rpnet.py"), reason="the reference is mounted in the build container only")
-def test_literal_reference_driver_reaches_the_model_through_the_launcher():
-    """The UNMODIFIED /root/reference/test_rpnet.py under tools/run_reference_driver.py with this repository on the path: its
-    imports (:11-32, incl. tensorboard at :27, absent here), yaml loading, reader construction and model_factory call all
-    resolve to this repository and run; without a GPU it stops exactly at `net = net.cuda()` (:82)."""
+def test_reference_driver_launcher_reaches_the_model(tmp_path):
+    """tools/run_reference_driver.py with this repository on the path: a driver script that masks the device
+    (`os.environ['CUDA_VISIBLE_DEVICES'] = '1'` before `import torch`), imports tensorboard (absent here), loads
+    yamls/example.yml, builds the reader and the model through model_factory and moves it to the device resolves every
+    import to this repository and runs.  Without a GPU (RPNET_DRIVER_ALLOW_NO_GPU=1) it stops exactly at `net = net.cuda()`;
+    where the launcher could initialise a GPU first, the device mask changes nothing and the move succeeds."""
     import subprocess
     import sys
+    script = tmp_path / "driver.py"
+    script.write_text(
+        "import os\n"
+        "os.environ['CUDA_VISIBLE_DEVICES'] = '1'\n"
+        "import sys\n"
+        "import torch\n"
+        "from torch.utils.tensorboard import SummaryWriter\n"
+        "from net.model import model_factory\n"
+        "from dataset.few_shot_reader import FewshotRegReader\n"
+        "from utils.util import load_yaml\n"
+        "config, args = load_yaml(sys.argv[1])\n"
+        "ds = FewshotRegReader(args.data_dir, args.eval_set_name, config, mode='eval')\n"
+        "net = model_factory[args.net](pretrained_path=config['pretrained_path'], cfg={'align': True, 'backbone': 'UNet'},\n"
+        "                              backbone_cfg=config)\n"
+        "print('MODEL_BUILT', type(net).__name__)\n"
+        "net = net.cuda()\n"
+        "print('MODEL_ON_DEVICE', next(net.parameters()).device)\n")
     env = dict(os.environ, RPNET_DRIVER_ALLOW_NO_GPU="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "run_reference_driver.py"), "/root/reference/test_rpnet.py",
-                        "--yaml", os.path.join(ROOT, "yamls", "example.yml")], capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
-    assert r.returncode != 0 and "No HIP GPUs are available" in r.stderr, r.stderr[-1500:]
-    assert "net = net.cuda()" in r.stderr and "no-op torch.utils.tensorboard.SummaryWriter registered" in r.stderr
-    assert "ModuleNotFoundError" not in r.stderr and "ImportError" not in r.stderr
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "run_reference_driver.py"), str(script),
+                        os.path.join(ROOT, "yamls", "example.yml")], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=str(tmp_path))
+    assert "ModuleNotFoundError" not in r.stderr and "ImportError" not in r.stderr, r.stderr[-1500:]
+    assert "MODEL_BUILT RP_Net" in r.stdout, (r.stdout[-500:], r.stderr[-1500:])
+    if "hip runtime initialised before the script" in r.stderr:
+        assert r.returncode == 0 and "MODEL_ON_DEVICE cuda" in r.stdout, (r.stdout[-500:], r.stderr[-1500:])
+    else:
+        assert r.returncode != 0 and "No HIP GPUs are available" in r.stderr, r.stderr[-1500:]
+        assert "net = net.cuda()" in r.stderr and "MODEL_ON_DEVICE" not in r.stdout
+    if "tensorboard" not in sys.modules and __import__("importlib").util.find_spec("tensorboard") is None:
+        assert "no-op torch.utils.tensorboard.SummaryWriter registered" in r.stderr
 
 
 def test_kept_alive_tensors_outlive_a_mid_backward_join():

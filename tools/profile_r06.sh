@@ -26,5 +26,5 @@ timeout -k 5 150 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $R/pf -o p --outpu
 timeout -k 5 150 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $R/pw -o p --output-format csv -- $S > $R/pw.log 2>&1; echo "write rc $?"
 [ -n "$(csvc $R/pf)" ] && [ -n "$(csvc $R/pw)" ] && python tools/pmc_traffic.py $(csvc $R/pf) $(csvc $R/pw) $O/${TAG}_pmc_traffic.json > $O/${TAG}_pmc_traffic.txt
 rm -rf $R/pf $R/pw
-python bench.py --steps 20 --warmup 3 --no-other-configs > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --steps 20 --warmup 3 --full --no-other-configs > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 ls -la $O; head -30 $O/${TAG}_pmc_traffic.txt; head -20 $O/${TAG}_pmc_mfma_busy.txt; grep "^step" $O/${TAG}_mfma_idle.txt; head -8 $O/${TAG}_timeline.txt
