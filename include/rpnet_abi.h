@@ -50,8 +50,9 @@ enum rpnet_status {
  * where a pointer is expected: hence the number); 105 round 5 (rpnet_refine_glue_*, rpnet_conv_up4*, rpnet_conv_wgrad_up4*,
  * rpnet_upconv_collapse_weights added; nothing existing changed).  A caller MUST zero-initialise rpnet_conv_desc (fields added
  * later are optional features that are off at zero) and SHOULD compare rpnet_version() with the RPNET_ABI_VERSION it was built
- * against. */
-#define RPNET_ABI_VERSION 108
+ * against.  109: rpnet_bn_eval_relu, rpnet_bn_eval_bwd, rpnet_conv1_dgrad_bn added (the gradient through eval-mode BatchNorm and the
+ * input images' gradient); nothing existing changed. */
+#define RPNET_ABI_VERSION 109
 int rpnet_version(void);
 const char* rpnet_last_error_string(void);
 
@@ -302,6 +303,15 @@ int rpnet_conv1_bn_bwd_rows(int N, int H, int W, int cout, int groups);
 int rpnet_conv1_bn_bwd_partial(const float* x, const float* w, const float* bias, const float* dz,
                                const float* stats /*[4][groups][cout]: scale, shift, mean, invstd*/, double* partial,
                                int N, int H, int W, int cout, int groups, rpnet_stream_t stream);
+/* input gradient of the same convolution (autograd of nn.Conv2d wrt the image): dx [N][H][W] (= [N][1][H][W]) =
+ * sum_taps sum_c w[c][tap] dy[pixel - tap offset][c], dy formed on the spot from dz, y, stats [4][groups][cout] and coef
+ * [groups][cout][2] as rpnet_conv1_wgrad_bn forms it (coef NULL = 0: eval mode, rpnet_bn_eval_bwd writes zeros there too).
+ * y == NULL: y is made again from x, w and bias (the train-mode path without y in memory, _CONV1_RECOMP).  One 16 x 16 tile
+ * per block with its halo of dy in LDS, fp32 sums in a fixed order: the same bits every run, no atomics.  cout % 32 == 0,
+ * cout <= 256; w (the filter [cout][1][3][3]) is always required. */
+int rpnet_conv1_dgrad_bn(const float* dz, const float* y, const float* stats, const float* coef, const float* w,
+                         const float* bias, const float* x, float* dx, int N, int H, int W, int cout, int groups,
+                         rpnet_stream_t stream);
 
 /* ---------------------------------------------------------------------- BatchNorm
  * Train-mode nn.BatchNorm2d + nn.ReLU(inplace) (net/modules.py:48-49,51-52,68-69),
@@ -359,6 +369,27 @@ int rpnet_bn_bwd(const float* dz, const float* y, const float* gamma, const floa
                  runs here; else the caller made the sums itself (the first layer: rpnet_conv1_bn_bwd_partial) */,
                  int pool_w, void* workspace, size_t workspace_bytes, const float* y_dec /* reserved */, int y_dec_stride,
                  rpnet_stream_t stream);
+
+/* Eval-mode nn.BatchNorm2d + nn.ReLU with a gradient (model.eval(), autograd on): the running statistics are used and left
+ * unchanged (no running buffer, no num_batches_tracked is touched).
+ *   rpnet_bn_eval_relu  z [P][C] = relu(y scale + shift) (scale, shift [C]: rpnet_bn_eval_affine) and
+ *                       *out_absmax = max(*out_absmax, max z) — an eval-mode output has no a-priori bound, so fp16 consumers
+ *                       take their tensor scale from this measurement (rpnet_split_f16 with a_is_bound), never from the
+ *                       train-mode bound of rpnet_bn_act_scale.  C % 4 == 0.
+ *   rpnet_bn_eval_bwd   dz -> dy = scale dz [y scale + shift > 0] (nothing subtracted: no batch-mean term), dgamma = sum dz m xhat,
+ *                       dbeta = sum dz m with xhat = (y - mean) invstd of the RUNNING statistics (mean, invstd, scale, shift
+ *                       [groups][C]: the same values repeated per group; dgamma, dbeta summed over groups, `accumulate` as
+ *                       rpnet_bn_bwd).  Outputs as rpnet_bn_bwd: dy fp32 (may be NULL) and / or dy_split planes; fp16 planes
+ *                       (planes 1 or 2) with the tensor scale from the rigorous bound |dy_c| <= |scale_c| max |dz m| gathered
+ *                       by the reduction pass.  Both NULL: the reduction only; the coefficients at workspace +
+ *                       rpnet_bn_bwd_coef_offset are then ZERO (rpnet_conv1_wgrad_bn / rpnet_conv1_dgrad_bn form dy from them).
+ *                       Workspace: rpnet_bn_workspace_bytes. */
+int rpnet_bn_eval_relu(const float* y, const float* scale, const float* shift, float* z, float* out_absmax, size_t P, int C,
+                       rpnet_stream_t stream);
+int rpnet_bn_eval_bwd(const float* dz, const float* y, const float* scale, const float* shift, const float* mean,
+                      const float* invstd, float* dy, void* dy_split, int planes, float* split_scale, float* dgamma,
+                      float* dbeta, int N, int HW, int C, int groups, int accumulate, void* workspace, size_t workspace_bytes,
+                      rpnet_stream_t stream);
 
 /* conv + bias + ReLU without BatchNorm (vgg.Encoder, net/vgg.py:39-58) — backward pieces:
  * dy = dz * [z > 0] (z may be NULL: no ReLU behind the conv) and db[c] = sum_pixels dy[p][c] */

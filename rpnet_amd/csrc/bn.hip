@@ -729,6 +729,64 @@ static int elt_grid(size_t total4) {
     return (int)(b > 2048 * 4 ? 2048 * 4 : (b < 1 ? 1 : b));
 }
 
+// ---- Eval-mode BatchNorm + ReLU with a gradient (nn.BatchNorm2d under model.eval(): the running statistics, which the pass
+// leaves unchanged).  Forward: z = relu(y scale + shift) with the measured max |z| (no a-priori bound exists for running
+// statistics).  Backward: the reduction pass of the train-mode backward (bn_bwd_partial, with mean / invstd = the running
+// ones) gives dbeta = sum dz m and dgamma = sum dz m xhat; the finalize below writes ZERO coefficients — there is no batch-mean
+// term — so the train-mode apply passes write dy = scale (dz m - 0 - xhat 0) = scale dz m, bit for bit.
+__global__ __launch_bounds__(256) void bn_eval_relu_kernel(const float* __restrict__ y, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, float* __restrict__ z,
+                                                            float* __restrict__ out_absmax, size_t total4, const FastDiv fc) {
+    RPNET_PASS_PRIORITY();
+    __shared__ float red4[4];
+    float m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
+        const int c4 = (int)fc.mod((unsigned)i);
+        const f32x4 v = reinterpret_cast<const f32x4*>(y)[i];
+        const f32x4 sc = reinterpret_cast<const f32x4*>(scale)[c4];
+        const f32x4 sh = reinterpret_cast<const f32x4*>(shift)[c4];
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { o[k] = fmaxf(v[k] * sc[k] + sh[k], 0.f); m = fmaxf(m, o[k]); }
+        reinterpret_cast<f32x4*>(z)[i] = o;
+    }
+    m = block_max256(m, red4);
+    // z >= 0: the bit patterns of non-negative floats order as unsigned integers
+    if (out_absmax && threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(out_absmax), __float_as_uint(m));
+}
+
+// dgamma / dbeta (summed over groups), coef = 0 and bound[c] = |scale_c| max |dz m| — the train-mode bound of bn_bwd_finalize
+// without its mean terms (|dy| = |scale dz m|; 1.0001 covers the rounding of the product)
+__global__ __launch_bounds__(256) void bn_eval_bwd_finalize(const double* __restrict__ partial, int nblk, int C, int G,
+                                                            float* coef, float* dgamma, float* dbeta, int accumulate,
+                                                            const float* __restrict__ pmax, const float* __restrict__ scale,
+                                                            float* __restrict__ bound) {
+    RPNET_PASS_PRIORITY();
+    __shared__ double red4[8];
+    __shared__ float redm[4];
+    const int c = blockIdx.x, lane = threadIdx.x;
+    double tg = 0, tb = 0;
+    float bnd = 0.f;
+    for (int g = 0; g < G; ++g) {
+        double s1 = 0, s2 = 0;
+        float mx = 0.f;
+        for (int b = lane; b < nblk; b += 256) {
+            const double* p = partial + ((size_t)(g * nblk + b) * C + c) * 2;
+            s1 += p[0]; s2 += p[1];
+            if (pmax) mx = fmaxf(mx, pmax[(size_t)(g * nblk + b) * C + c]);
+        }
+        s1 = block_sum256(s1, red4); s2 = block_sum256(s2, red4 + 4);
+        if (pmax) bnd = fmaxf(bnd, fabsf(scale[g * C + c]) * block_max256(mx, redm));
+        if (lane == 0) { coef[(g * C + c) * 2] = 0.f; coef[(g * C + c) * 2 + 1] = 0.f; }
+        tb += s1; tg += s2;
+    }
+    if (pmax && lane == 0) bound[c] = bnd * 1.0001f;
+    if (lane == 0) {
+        if (accumulate) { dgamma[c] += (float)tg; dbeta[c] += (float)tb; }
+        else { dgamma[c] = (float)tg; dbeta[c] = (float)tb; }
+    }
+}
+
 }  // namespace rpnet
 
 extern "C" size_t rpnet_bn_workspace_bytes(int C, int groups) {
@@ -957,4 +1015,68 @@ extern "C" int rpnet_bn_bwd(const float* dz, const float* y, const float* gamma,
     hipLaunchKernelGGL(bn_bwd_apply, dim3(elt_grid(total4)), dim3(256), 0, s, dz, ysrc, scale, shift, mean, invstd,
                        (const float*)coef, dy, total4, C, group4, FastDiv(C / 4), FastDiv((unsigned)group4));
     return check_launch("bn_bwd");
+}
+
+extern "C" int rpnet_bn_eval_relu(const float* y, const float* scale, const float* shift, float* z, float* out_absmax, size_t P,
+                                  int C, rpnet_stream_t stream) {
+    using namespace rpnet;
+    RPNET_REQUIRE(y && scale && shift && z, RPNET_ERR_ARG, "bn_eval_relu: null pointer");
+    RPNET_REQUIRE(C % 4 == 0 && C > 0, RPNET_ERR_SHAPE, "bn_eval_relu: C=%d must be a multiple of 4", C);
+    const size_t total4 = P * C / 4;
+    RPNET_REQUIRE(total4 < kIndex32, RPNET_ERR_SHAPE, "bn_eval_relu: %zu 16-byte elements do not fit the 32-bit index arithmetic", total4);
+    if (!total4) return 0;
+    hipLaunchKernelGGL(bn_eval_relu_kernel, dim3(elt_grid(total4)), dim3(256), 0, (hipStream_t)stream, y, scale, shift, z, out_absmax,
+                       total4, FastDiv(C / 4));
+    return check_launch("bn_eval_relu");
+}
+
+extern "C" int rpnet_bn_eval_bwd(const float* dz, const float* y, const float* scale, const float* shift, const float* mean,
+                                 const float* invstd, float* dy, void* dy_split, int planes, float* split_scale, float* dgamma,
+                                 float* dbeta, int N, int HW, int C, int groups, int accumulate, void* workspace,
+                                 size_t workspace_bytes, rpnet_stream_t stream) {
+    using namespace rpnet;
+    const YSrc ysrc{y};
+    RPNET_REQUIRE(dz && y && scale && shift && mean && invstd && dgamma && dbeta && workspace, RPNET_ERR_ARG,
+                  "bn_eval_bwd: null pointer");
+    RPNET_REQUIRE(!dy_split || (planes >= 1 && planes <= 3 && C % 8 == 0), RPNET_ERR_SHAPE, "bn_eval_bwd: split planes=%d C=%d",
+                  planes, C);
+    if (int rc = bn_check("bn_eval_bwd", N, HW, C, groups)) return rc;
+    RPNET_REQUIRE(workspace_bytes >= rpnet_bn_workspace_bytes(C, groups), RPNET_ERR_WORKSPACE, "bn_eval_bwd: workspace too small");
+    const long R = (long)(N / groups) * HW;
+    const size_t total4 = (size_t)N * HW * C / 4, group4 = total4 / groups;
+    RPNET_REQUIRE(total4 < kIndex32, RPNET_ERR_SHAPE, "bn: %zu 16-byte elements do not fit the 32-bit index arithmetic of the passes", total4);
+    const BnGeom gm = bn_geom(R, C);
+    hipStream_t s = (hipStream_t)stream;
+    double* partial = (double*)workspace;
+    float* coef = (float*)((char*)workspace + (size_t)groups * bn_max_blocks(C) * C * 2 * sizeof(double));
+    const bool f16 = dy_split && planes <= 2;
+    RPNET_REQUIRE(!f16 || split_scale, RPNET_ERR_ARG, "bn_eval_bwd: fp16 planes (1 or 2) need the scale output");
+    float* pmax = f16 ? coef + (size_t)groups * C * 2 : nullptr;
+    float* bound = f16 ? pmax + (size_t)groups * bn_max_blocks(C) * C : nullptr;
+    if (bn_lds_window() == 64)
+        hipLaunchKernelGGL(bn_bwd_partial<64>, dim3(gm.nblk, groups), dim3(256), 0, s, dz, ysrc, scale, shift, mean, invstd, partial,
+                           pmax, R, C, gm);
+    else
+        hipLaunchKernelGGL(bn_bwd_partial<256>, dim3(gm.nblk, groups), dim3(256), 0, s, dz, ysrc, scale, shift, mean, invstd, partial,
+                           pmax, R, C, gm);
+    hipLaunchKernelGGL(bn_eval_bwd_finalize, dim3(C), dim3(256), 0, s, (const double*)partial, gm.nblk, C, groups, coef, dgamma,
+                       dbeta, accumulate, (const float*)pmax, scale, bound);
+    // dy == NULL and dy_split == NULL: dgamma, dbeta and the (zero) coefficients only, for a consumer that forms dy itself
+    // (rpnet_conv1_wgrad_bn, rpnet_conv1_dgrad_bn)
+    if (!dy && !dy_split) return check_launch("bn_eval_bwd");
+    if (dy_split) {
+        const size_t total8 = total4 / 2, pe = (size_t)N * HW * C;
+#define RPNET_BN_EVAL_APPLY(NP_)                                                                                            \
+    hipLaunchKernelGGL(bn_bwd_apply_split<NP_>, dim3(elt_grid(total8)), dim3(256), 0, s, dz, ysrc, scale, shift, mean, invstd,   \
+                       (const float*)coef, dy, (unsigned short*)dy_split, total8, C, group4 / 2, pe, (const float*)bound,     \
+                       split_scale, FastDiv(C / 8), FastDiv((unsigned)(group4 / 2)))
+        if (planes == 3) RPNET_BN_EVAL_APPLY(3);
+        else if (planes == 2) RPNET_BN_EVAL_APPLY(2);
+        else RPNET_BN_EVAL_APPLY(1);
+#undef RPNET_BN_EVAL_APPLY
+        return check_launch("bn_eval_bwd");
+    }
+    hipLaunchKernelGGL(bn_bwd_apply, dim3(elt_grid(total4)), dim3(256), 0, s, dz, ysrc, scale, shift, mean, invstd,
+                       (const float*)coef, dy, total4, C, group4, FastDiv(C / 4), FastDiv((unsigned)group4));
+    return check_launch("bn_eval_bwd");
 }

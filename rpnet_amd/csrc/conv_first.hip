@@ -637,6 +637,77 @@ __global__ __launch_bounds__(64) void conv1_wgrad_final(const float* __restrict_
     if (lane == 0) dw[i] = (float)s;
 }
 
+// Input gradient of the layer (autograd of nn.Conv2d(1, Cout, 3, padding=1) wrt its input):
+//   dx[n, h, w] = sum_{ky, kx} sum_c w[c][ky][kx] dy[n, h + 1 - ky, w + 1 - kx, c]
+// with dy formed on the spot from the BatchNorm + ReLU output gradient dz, y (or y made again from x: conv1_quad), stats and coef
+// exactly as conv1_wgrad_partial forms it.  Block = a 16 x 16 tile of one image; dy of the 18 x 18 halo is built in LDS, 32
+// channels at a time ([channel][pixel]: a thread's tap reads are consecutive across the wave), and each thread sums its pixel's
+// 9 x Cout products in a fixed order (channel chunks, taps, channels): deterministic, no atomics.
+constexpr int kC1dTile = 16, kC1dHalo = kC1dTile + 2, kC1dPix = kC1dHalo * kC1dHalo, kC1dChunk = 32;
+
+template <bool RECOMP>
+__global__ __launch_bounds__(256) void conv1_dgrad_bn_kernel(const float* __restrict__ dz, const float* __restrict__ ybn,
+                                                              const float* __restrict__ stats, const float* __restrict__ coef,
+                                                              const float* __restrict__ w, const float* __restrict__ bias,
+                                                              const float* __restrict__ x, float* __restrict__ dx,
+                                                              const int N, const int H, const int W, const int Cout, const int groups) {
+    RPNET_PASS_PRIORITY();
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* const wl = lds;                          // [9][Cout] filter + [Cout] bias (conv1_load_filter)
+    float* const prm = wl + 10 * Cout;              // [6][Cout]: scale, shift, mean, invstd, c1, c2 of this image's group
+    float* const dyl = prm + 6 * Cout;              // [kC1dChunk][kC1dPix]
+    const int t = threadIdx.x;
+    const int n = blockIdx.z, g = n / (N / groups);
+    const int h0 = blockIdx.y * kC1dTile, w0 = blockIdx.x * kC1dTile;
+    conv1_load_filter(wl, w, bias, Cout);
+    for (int i = t; i < Cout; i += 256) {
+        const int GC = groups * Cout, o = g * Cout + i;
+        prm[i] = stats[o]; prm[Cout + i] = stats[GC + o]; prm[2 * Cout + i] = stats[2 * GC + o]; prm[3 * Cout + i] = stats[3 * GC + o];
+        prm[4 * Cout + i] = coef ? coef[o * 2] : 0.f;
+        prm[5 * Cout + i] = coef ? coef[o * 2 + 1] : 0.f;
+    }
+    const unsigned nb = (unsigned)n * (unsigned)H * (unsigned)W;
+    const int ty = t / kC1dTile, tx = t % kC1dTile;
+    float acc = 0.f;
+    constexpr int Q = kC1dChunk / 4;
+    for (int c0 = 0; c0 < Cout; c0 += kC1dChunk) {
+        __syncthreads();      // the filter / parameters are in place; the previous chunk's readers are done
+        for (int i = t; i < kC1dPix * Q; i += 256) {
+            const int pix = i / Q, q = i - pix * Q;
+            const int hy = h0 - 1 + pix / kC1dHalo, hx = w0 - 1 + pix % kC1dHalo;
+            f32x4 r = {0.f, 0.f, 0.f, 0.f};
+            if (hy >= 0 && hy < H && hx >= 0 && hx < W) {
+                const size_t p = (size_t)nb + (size_t)hy * W + hx;
+                const int c = c0 + q * 4;
+                const f32x4 d = *reinterpret_cast<const f32x4*>(dz + p * Cout + c);
+                f32x4 v;
+                if constexpr (RECOMP) v = conv1_quad(x, wl, Cout, c / 4, nb, hy, hx, H, W);
+                else v = *reinterpret_cast<const f32x4*>(ybn + p * Cout + c);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float sc = prm[c + k], sh = prm[Cout + c + k], mu = prm[2 * Cout + c + k], is = prm[3 * Cout + c + k];
+                    const float dm = (v[k] * sc + sh > 0.f) ? d[k] : 0.f;
+                    r[k] = sc * (dm - prm[4 * Cout + c + k] - (v[k] - mu) * is * prm[5 * Cout + c + k]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dyl[(q * 4 + k) * kC1dPix + pix] = r[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int pix = (ty + 2 - ky) * kC1dHalo + tx + 2 - kx;
+                const float* wt = wl + (ky * 3 + kx) * Cout + c0;
+#pragma unroll 8
+                for (int c = 0; c < kC1dChunk; ++c) acc = __builtin_fmaf(wt[c], dyl[c * kC1dPix + pix], acc);
+            }
+    }
+    const int oy = h0 + ty, ox = w0 + tx;
+    if (oy < H && ox < W) dx[(size_t)nb + (size_t)oy * W + ox] = acc;
+}
+
 constexpr int kConv1WgradBlocks = 1024;
 
 // the four-pixel strip kernels: rows are whole strips, statistic groups too, 32-bit pixel arithmetic
@@ -797,4 +868,24 @@ extern "C" int rpnet_conv1_bn_bwd_partial(const float* x, const float* w, const 
         hipLaunchKernelGGL(conv1_bn_bwd_partial_kernel, dim3(nblk, groups), dim3(256), lds, (hipStream_t)stream, x, w, bias, dz, stats,
                            partial, N, H, W, cout, groups);
     return check_launch("conv1_bn_bwd_partial");
+}
+
+extern "C" int rpnet_conv1_dgrad_bn(const float* dz, const float* y, const float* stats, const float* coef, const float* w,
+                                    const float* bias, const float* x, float* dx, int N, int H, int W, int cout, int groups,
+                                    rpnet_stream_t stream) {
+    using namespace rpnet;
+    RPNET_REQUIRE(dz && stats && w && dx && (y || x), RPNET_ERR_ARG, "conv1_dgrad_bn: null pointer (y, or the image x to make it again)");
+    RPNET_REQUIRE(cout % kC1dChunk == 0 && cout <= 256, RPNET_ERR_SHAPE, "conv1_dgrad_bn: cout=%d must be a multiple of %d", cout, kC1dChunk);
+    RPNET_REQUIRE(N >= 1 && H >= 1 && W >= 1 && groups >= 1 && N % groups == 0, RPNET_ERR_SHAPE, "conv1_dgrad_bn: N=%d H=%d W=%d groups=%d",
+                  N, H, W, groups);
+    RPNET_REQUIRE((size_t)N * H * W < ((size_t)1 << 31) && N <= 65535, RPNET_ERR_SHAPE, "conv1_dgrad_bn: %d x %d x %d pixels", N, H, W);
+    const dim3 grid(cdiv(W, kC1dTile), cdiv(H, kC1dTile), N);
+    const size_t lds = ((size_t)16 * cout + (size_t)kC1dChunk * kC1dPix) * sizeof(float);
+    if (y)
+        hipLaunchKernelGGL(conv1_dgrad_bn_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, dz, y, stats, coef, w, bias, x, dx,
+                           N, H, W, cout, groups);
+    else
+        hipLaunchKernelGGL(conv1_dgrad_bn_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, dz, y, stats, coef, w, bias, x, dx,
+                           N, H, W, cout, groups);
+    return check_launch("conv1_dgrad_bn");
 }

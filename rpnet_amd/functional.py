@@ -918,7 +918,10 @@ class ConvBnRelu(Function):
         cout = weight.shape[0]
         first = weight.shape[1] == 1 and weight.shape[2] == 3  # Cin = 1 direct convolution
         z = _empty((N, H, W, cout), x0)
-        if not training:
+        # eval mode with a gradient (produced["eval_grad"], set by conv_bn_relu_op): the convolution writes the pre-BatchNorm y
+        # for the backward, the running-statistics affine and ReLU follow in their own pass (rpnet_bn_eval_relu)
+        bn_eval = not training
+        if bn_eval and not produced.get("eval_grad"):
             aff = getattr(pw, "eval_affine", None)     # the folded BatchNorm lives as long as the layer's packed weights
             if aff is None:
                 aff = (_empty((cout,), x0), _empty((cout,), x0))
@@ -1010,14 +1013,16 @@ class ConvBnRelu(Function):
             ctx.eval_mode = True
             return z
         # the first layer on fp16 planes whose only consumer reads the planes: y is summed, never written (see _CONV1_RECOMP)
-        recomp = bool(first and _CONV1_RECOMP and f16_mode() and cout % 8 == 0 and 256 % (cout // 8) == 0 and out_split is True
+        if bn_eval:
+            groups = 1       # running statistics: one affine for every image
+        recomp = bool(not bn_eval and first and _CONV1_RECOMP and f16_mode() and cout % 8 == 0 and 256 % (cout // 8) == 0 and out_split is True
                       and produced.get("z_unused") and not produced.get("pool_req") and _CONV1_BN_FUSE
                       and query("rpnet_conv1_stats_blocks", N, H, W, cout, groups) > 0)
         y = None if recomp else _empty((N, H, W, cout), x0)
         stats = _empty((4, groups, cout), x0)  # scale, shift, mean, invstd
         fused, xs, sx, sx1 = 0, None, None, None
         if first:      # batch statistics out of the same launch (one partial row per block and group)
-            fused = query("rpnet_conv1_stats_blocks", N, H, W, cout, groups)
+            fused = 0 if bn_eval else query("rpnet_conv1_stats_blocks", N, H, W, cout, groups)
             part = torch.empty(groups * fused * cout * 2, device=x0.device, dtype=torch.float64) if fused else None
             call("rpnet_conv1_fwd", ptr(x0), ptr(weight), ptr(bias), ptr(y), None, None, N, H, W, cout, None, ptr(part), groups)
         else:
@@ -1047,7 +1052,7 @@ class ConvBnRelu(Function):
                 d.split_planes = np_
             else:
                 d = _desc(x0, x1, pw.wp, bias, in_scale, in_mode, y, None, N, H, W, pw.taps, upsample, groups)
-            fused = query("rpnet_conv_up4_stats_blocks" if up4 else "rpnet_conv_stats_blocks", C.byref(d))
+            fused = 0 if bn_eval else query("rpnet_conv_up4_stats_blocks" if up4 else "rpnet_conv_stats_blocks", C.byref(d))
             if fused:  # batch statistics come out of the conv epilogue: y is not re-read
                 part = torch.empty(groups * fused * cout * 2, device=x0.device, dtype=torch.float64)
                 d.stats_partial = ptr(part)
@@ -1055,6 +1060,10 @@ class ConvBnRelu(Function):
                 _cup4(d, 1)
             else:
                 _cconv("rpnet_conv_fwd", d)
+        if bn_eval:
+            return ConvBnRelu._eval_grad_tail(ctx, x0, x1, in_scale, weight, bias, gamma, beta, running_mean, running_var, y,
+                                              z, pw, upsample, in_mode, first, out_split, produced, xs, sx, sx1,
+                                              (not first) and up4)
         _order_wait(gamma.data_ptr())      # the running statistics: after the other chain's update of this module
         if fused:
             call("rpnet_bn_stats_from_partial", ptr(part), fused, N, H * W, cout, groups, ptr(gamma), ptr(beta),
@@ -1124,11 +1133,41 @@ class ConvBnRelu(Function):
         return z
 
     @staticmethod
+    def _eval_grad_tail(ctx, x0, x1, in_scale, weight, bias, gamma, beta, running_mean, running_var, y, z, pw, upsample, in_mode,
+                        first, out_split, produced, xs, sx, sx1, up4):
+        """eval mode with a gradient, behind the convolution that wrote y: stats [4][1][cout] = (scale, shift, running mean,
+        running invstd), z = relu(y scale + shift) with its measured maximum, the output's operand planes / fp16 scale from that
+        measurement (the running statistics give no a-priori bound), and what the backward needs"""
+        N, H, W, cout = y.shape
+        stats = _empty((4, 1, cout), y)
+        call("rpnet_bn_eval_affine", ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), BN_EPS, ptr(stats[0]),
+             ptr(stats[1]), cout)
+        stats[2, 0].copy_(running_mean)
+        torch.rsqrt(running_var + BN_EPS, out=stats[3, 0])
+        mx = torch.zeros(1, device=y.device, dtype=torch.float32)
+        call("rpnet_bn_eval_relu", ptr(y), ptr(stats[0]), ptr(stats[1]), ptr(z), ptr(mx), N * H * W, cout)
+        ARITH[("bn_relu", "eval mode, with a gradient")] += 1
+        if f16_mode() and cout % 32 == 0 and bool(out_split) and (_CORR16 or out_split != "corr"):
+            if out_split in (True, "corr"):
+                produced["p16"], produced["scale"] = split_f16(z, mx, a_is_bound=True)
+            else:
+                sz = torch.empty(1, device=y.device, dtype=torch.float32)
+                call("rpnet_pow2_scale", ptr(mx), ptr(sz))
+                produced["scale"] = sz
+        ctx.save_for_backward(x0, x1, in_scale, weight, gamma, y, stats)
+        ctx.yshape = (N, H, W, cout)
+        ctx.pw, ctx.cfg, ctx.eval_mode, ctx.pool, ctx.bn_eval = pw, (1, upsample, in_mode, first), False, False, True
+        ctx.up4 = up4
+        ctx.bias, ctx.beta, ctx.xs, ctx.sx, ctx.sx1 = bias, beta, xs, sx, sx1
+        ctx.opts = (_ASYNC["on"], _MASK_SKIP)
+        return z
+
+    @staticmethod
     @once_differentiable
     def backward(ctx, dz):
         if ctx.eval_mode:
-            raise NotImplementedError("rpnet_amd: backward through eval-mode BatchNorm is not implemented "
-                                      "(the reference only evaluates under torch.no_grad, test_rpnet.py:163)")
+            raise RuntimeError("rpnet_amd: an eval-mode layer made without a gradient-capable forward reached backward "
+                               "(conv_bn_relu_op decides from torch.is_grad_enabled() and requires_grad at call time)")
         x0, x1, in_scale, weight, gamma, y, stats = ctx.saved_tensors
         async_on, skip_on = getattr(ctx, "opts", (None, None))
         pw = ctx.pw
@@ -1161,8 +1200,13 @@ class ConvBnRelu(Function):
             call("rpnet_conv1_wgrad_bn", ptr(x0), ptr(dz), None, ptr(stats), coef, ptr(dw), N, H, W, cout, groups, ptr(ws2), wb,
                  ptr(weight), ptr(bias))
             dw = _accumulate_direct(weight, dw, async_on)
+            dx0 = None
+            if ctx.needs_input_grad[0]:     # the image's gradient, y made again from the image as above
+                dx0 = _empty(x0.shape, dz)
+                call("rpnet_conv1_dgrad_bn", ptr(dz), None, ptr(stats), coef, ptr(weight), ptr(bias), ptr(x0), ptr(dx0), N, H, W, cout,
+                     groups)
             db = None if _direct(bias, async_on) else torch.zeros_like(gamma)
-            return None, None, None, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None
+            return dx0, None, None, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None
         # which forms of dy the two consumers (wgrad, dgrad) want: split-bf16 planes and / or fp32
         np_ = ctx.xs[0].shape[0] if ctx.xs is not None else 0
         need_d = not first and (ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]))
@@ -1178,15 +1222,22 @@ class ConvBnRelu(Function):
             dy = None
         if ctx.pool and (dys is None or dz.shape[1] * 2 != H):
             raise RuntimeError("rpnet_amd: the pooled BatchNorm backward needs dy as split planes and the pooled gradient")
-        direct = _direct(gamma, async_on) and _direct(beta, async_on)     # straight into the gradient bucket, no AccumulateGrad add
+        bn_eval = getattr(ctx, "bn_eval", False)
+        # straight into the gradient bucket, no AccumulateGrad add (eval mode: the conv bias gradient is made from dbeta below)
+        direct = _direct(gamma, async_on) and _direct(beta, async_on) and not bn_eval
         dgamma, dbeta = (None, None) if direct else (_empty((cout,), y), _empty((cout,), y))
-        ARITH[("bn_bwd", "own reduction pass")] += 1
+        ARITH[("bn_bwd", "eval mode" if bn_eval else "own reduction pass")] += 1
         if direct:
             _order_wait(gamma.data_ptr())  # gamma.grad / beta.grad: after the other chain's accumulation into them
-        call("rpnet_bn_bwd", ptr(dz), ptr(y), ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]),
-             ptr(dy), ptr(dys), np_ if dys is not None else 0, ptr(sdy), ptr(gamma.grad if direct else dgamma),
-             ptr(beta.grad if direct else dbeta), N, H * W, cout, groups, 1 if direct else 0, None, None, 0,
-             W if ctx.pool else 0, ptr(ws), wsb, None, 0)
+        if bn_eval:      # running statistics: dy = scale dz m, nothing subtracted; the coefficients in ws are zero
+            call("rpnet_bn_eval_bwd", ptr(dz), ptr(y), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(dy),
+                 ptr(dys), np_ if dys is not None else 0, ptr(sdy), ptr(dgamma), ptr(dbeta), N, H * W, cout, groups, 0,
+                 ptr(ws), wsb)
+        else:
+            call("rpnet_bn_bwd", ptr(dz), ptr(y), ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]),
+                 ptr(dy), ptr(dys), np_ if dys is not None else 0, ptr(sdy), ptr(gamma.grad if direct else dgamma),
+                 ptr(beta.grad if direct else dbeta), N, H * W, cout, groups, 1 if direct else 0, None, None, 0,
+                 W if ctx.pool else 0, ptr(ws), wsb, None, 0)
         if direct:
             _order_done(gamma.data_ptr())
         _tap("bn_bwd:dz,dy,dys,sdy,ws", weight, dz, dy, dys, sdy, ws)
@@ -1195,13 +1246,19 @@ class ConvBnRelu(Function):
         if first:
             wb = query("rpnet_conv1_wgrad_workspace_bytes", N, H, W, cout)
             ws2 = _ws(wb, y)
+            coef = ws.data_ptr() + query("rpnet_bn_bwd_coef_offset", cout, groups)
             if fuse1:
-                coef = ws.data_ptr() + query("rpnet_bn_bwd_coef_offset", cout, groups)
                 call("rpnet_conv1_wgrad_bn", ptr(x0), ptr(dz), ptr(y), ptr(stats), coef, ptr(dw), N, H, W, cout, groups,
                      ptr(ws2), wb, None, None)
             else:
                 call("rpnet_conv1_wgrad", ptr(x0), ptr(dy), ptr(dw), N, H, W, cout, ptr(ws2), wb)
             dw = _accumulate_direct(weight, dw, async_on)
+            if ctx.needs_input_grad[0]:
+                # the image's gradient (saliency, robustness checks): dy formed on the spot from dz, y and the coefficients of
+                # the reduction pass (zero in eval mode), so no fp32 dy is needed for it
+                dx0 = _empty(x0.shape, dz)
+                call("rpnet_conv1_dgrad_bn", ptr(dz), ptr(y), ptr(stats), coef, ptr(weight), None, None, ptr(dx0), N, H, W, cout,
+                     groups)
         else:
             # same gather descriptor as the forward (sources, up-sampling, x*mask factor); dy is the other operand
             if wsplit:       # both wgrad operands as split planes (the x*mask factor is already in xs)
@@ -1323,8 +1380,10 @@ class ConvBnRelu(Function):
                 dx1 = g1 if need1 else None
             if deferred:                  # no input gradient wanted: no dgrad to wait for
                 _release_wgrads(_WGRAD_DEFER - 1)
-        # conv bias in front of a train-mode BatchNorm: the gradient is analytically zero
-        db = None if _direct(bias, async_on) else torch.zeros_like(gamma)
+        if bn_eval:      # eval mode: d(bias) = sum over pixels of dy = scale dbeta (the running statistics do not absorb it)
+            db = _accumulate_direct(bias, stats[0, 0] * dbeta, async_on)
+        else:            # conv bias in front of a train-mode BatchNorm: the gradient is analytically zero
+            db = None if _direct(bias, async_on) else torch.zeros_like(gamma)
         return dx0, dx1, dscale, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1349,6 +1408,12 @@ def conv_bn_relu_op(x0, conv, bn, cache, training, x1=None, in_scale=None, in_mo
     produced = {"z_unused": bool(z_unused) and training and conv.weight.shape[0] % 64 == 0,
                 "pool": bool(pool) and training and _POOL_FUSE, "pool_req": bool(pool),
                 "defer_act": bool(defer_act) and training and not out_split}
+    if not training and torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (op0.x, None if op1 is None else op1.x, in_scale, conv.weight, conv.bias,
+                                                        bn.weight, bn.bias)):
+        # eval mode with a gradient (test-time fine-tuning with frozen statistics, image gradients): the gradient-capable form
+        # of the forward (ConvBnRelu._eval_grad_tail); under torch.no_grad the folded form of the inference path runs
+        produced["eval_grad"] = True
     z = ConvBnRelu.apply(op0.x, None if op1 is None else op1.x, in_scale, conv.weight, conv.bias, bn.weight, bn.bias,
                          bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None, pw, training, groups,
                          1 if upsample else 0, in_mode, out_split, (op0, op1), produced)

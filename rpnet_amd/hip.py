@@ -69,6 +69,7 @@ _SIGS = {
     "rpnet_conv1_bn_relu": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "rpnet_conv1_bn_bwd_rows": (ci, [ci, ci, ci, ci, ci]),
     "rpnet_conv1_bn_bwd_partial": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "rpnet_conv1_dgrad_bn": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "rpnet_bn_bwd_coef_offset": (cs, [ci, ci]),
     "rpnet_bn_workspace_bytes": (cs, [ci, ci]),
     "rpnet_bn_stats": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, cs, vp]),
@@ -76,6 +77,8 @@ _SIGS = {
     "rpnet_bn_relu": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp]),
     "rpnet_bn_act_scale": (ci, [vp, vp, vp, ci, ci, ci, ci, vp]),
     "rpnet_bn_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, cs, vp, ci, vp]),
+    "rpnet_bn_eval_relu": (ci, [vp, vp, vp, vp, vp, cs, ci, vp]),
+    "rpnet_bn_eval_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, cs, vp]),
     "rpnet_bias_relu_bwd_workspace_bytes": (cs, [ci]),
     "rpnet_bias_relu_bwd": (ci, [vp, vp, vp, vp, cs, ci, vp, cs, vp]),
     "rpnet_maxpool3_fwd": (ci, [vp, vp, ci, ci, ci, ci, ci, vp]),
@@ -126,7 +129,7 @@ _SIGS = {
     "rpnet_debug_mfma_spin": (ci, [ci, ci, C.c_longlong, vp, vp]),
 }
 ABI_SYMBOLS = tuple(_SIGS)
-ABI_VERSION = 108      # RPNET_ABI_VERSION of include/rpnet_abi.h
+ABI_VERSION = 109      # RPNET_ABI_VERSION of include/rpnet_abi.h
 
 
 def lib_path():

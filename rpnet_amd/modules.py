@@ -415,8 +415,11 @@ class RP_Net(nn.Module):
         self.backbone_cfg = backbone_cfg
         # serving switch (off by default): in eval mode keep the packed weights and folded BatchNorm affines between
         # calls; the caller promises not to change parameters / running statistics meanwhile (rpnet_amd.graph sets it:
-        # a captured graph assumes static weights anyway).  `net._cache.clear()` drops the packs.
+        # a captured graph assumes static weights anyway).  `net._cache.clear()` drops the packs.  An eval-mode call with
+        # autograd on (test-time fine-tuning: the weights change between calls) rebuilds them whatever this switch says, and
+        # so does the first frozen call after it.
         self.freeze_packs = False
+        self._packs_from_grad_call = False
         # test / diagnostic hook (off by default): teacher forcing of the refinement loop — {i: mask [B,h,w]} replaces the
         # mask fed INTO iteration i (the loop's own thresholded prediction of iteration i-1, net/rp_net.py:308-311), so
         # that one flipped pixel at the 0.5 threshold cannot compound across iterations when two arithmetics are compared
@@ -473,7 +476,10 @@ class RP_Net(nn.Module):
         h, w = H // self.scale, W // self.scale
         cache = self._cache
         RF.reset_async()
-        if self.training or not self.freeze_packs:
+        grad_eval = not self.training and torch.is_grad_enabled()
+        repack = self.training or not self.freeze_packs or grad_eval or self._packs_from_grad_call
+        self._packs_from_grad_call = grad_eval
+        if repack:
             cache.clear()  # packed weights live for one forward only (never reused across optimizer steps)
 
         # ---- features: support and query through the encoder, separate BN statistics (:245-258)
@@ -494,7 +500,7 @@ class RP_Net(nn.Module):
                 pred_key = (self._serial, RF.conv_math(), ns, B, H, W, self.num_iter, n_ways, n_shots, self.forced_masks is not None)
                 RF.pred_begin(supp.device, pred_key, allow=not getattr(self, "_pred_redo", False))
         planes = RF.pack_planes()
-        if _PREPACK and planes and (self.training or not self.freeze_packs):
+        if _PREPACK and planes and repack:
             # every 3x3 layer's operand pack of this forward in one launch per kernel instead of two launches per layer
             # (the two up_conv layers on their collapsed four-tap packs, RF._UP4)
             # (round 6: eval mode too — the collapsed form's epilogue carries the folded BatchNorm affine)
