@@ -51,8 +51,9 @@ enum rpnet_status {
  * rpnet_upconv_collapse_weights added; nothing existing changed).  A caller MUST zero-initialise rpnet_conv_desc (fields added
  * later are optional features that are off at zero) and SHOULD compare rpnet_version() with the RPNET_ABI_VERSION it was built
  * against.  109: rpnet_bn_eval_relu, rpnet_bn_eval_bwd, rpnet_conv1_dgrad_bn added (the gradient through eval-mode BatchNorm and the
- * input images' gradient); nothing existing changed. */
-#define RPNET_ABI_VERSION 109
+ * input images' gradient); nothing existing changed.  110: rpnet_seg_tally added (masks and Dice tallies of an evaluation call);
+ * nothing existing changed. */
+#define RPNET_ABI_VERSION 110
 int rpnet_version(void);
 const char* rpnet_last_error_string(void);
 
@@ -562,6 +563,24 @@ int rpnet_objective_fwd(const float* const* logits, const float* weights, int n,
 int rpnet_objective_bwd(const float* const* logits, float* const* dlogits, const float* weights, int n, const int64_t* labels,
                         const float* stats, const float* gscale, float* dextra, float extra_scale, int B, int K, int H, int W,
                         rpnet_stream_t stream);
+
+/* Segmentation masks and Dice tallies of an evaluation call in ONE launch (csrc/segtally.hip; rpnet_amd/volume.py) — what the
+ * reference's driver does per logit tensor with softmax(dim=1)[:, 1].cpu(), `> 0.5` and utils/util.py:379-390 on the host
+ * (test_rpnet.py:189-246).  `src` / `src_kind`: HOST arrays of S <= 16 device pointers and their kinds (as rpnet_dice_ce_multi_fwd
+ * takes its logit tensors: no table in device memory, nothing to copy per call): kind 0 = logits [N][K][H][W], kind 1 = a 0/1 fp32
+ * mask [N][H][W] (`> 0.5f` = class 1; the driver's affine baseline).  A pixel of a logits source belongs to foreground class c
+ * (1 <= c < K) iff softmax(logits)[c] > 0.5f, computed as rpnet_refine_glue_fwd computes the mask it feeds back (max-subtracted
+ * expf, fp32 division), else to 0; an exact tie is background.
+ *   labels  [N][H][W] class ids 0 .. K-1 (other values count for no class), or NULL
+ *   n_valid DEVICE scalar: images n >= *n_valid (clamped to 0 .. N) are ignored — not counted, their mask bytes not written; read
+ *           by the kernel, so that a captured launch serves the ragged last batch of a volume
+ *   counts  [S][K-1][3] += {|P and T|, |P|, |T|} per source and foreground class (caller-zeroed; 64-bit atomic adds of integers:
+ *           deterministic); NULL iff labels is NULL
+ *   mask    [N][H][W] the class id of source `mask_src`, or NULL
+ * K <= 4; W a multiple of 16 (16-byte loads along W); N*K*H*W < 2^32; every source and `labels` 16-byte aligned, `mask` 4-byte.
+ * N == 0 or H*W == 0: success, nothing launched.  Every source value is read once. */
+int rpnet_seg_tally(const float* const* src, const int32_t* src_kind, int S, const int32_t* labels, const int32_t* n_valid,
+                    unsigned long long* counts, uint8_t* mask, int mask_src, int N, int K, int H, int W, rpnet_stream_t stream);
 
 /* alignLoss pieces: arg-max class masks of the low-res prediction with their pixel
  * counts (net/rp_net.py:412-417) — masks [B][K][hw] (0/1), counts [B][K], keep [K][B] (optional; 1 where the count is positive:

@@ -122,6 +122,7 @@ _SIGS = {
     "rpnet_dice_ce_multi_bwd": (ci, [C.POINTER(vp), C.POINTER(vp), ci, vp, vp, vp, ci, ci, ci, ci, vp]),
     "rpnet_objective_fwd": (ci, [C.POINTER(vp), C.POINTER(cf), ci, vp, vp, cf, vp, vp, ci, ci, ci, ci, vp, cs, vp]),
     "rpnet_objective_bwd": (ci, [C.POINTER(vp), C.POINTER(vp), C.POINTER(cf), ci, vp, vp, vp, vp, cf, ci, ci, ci, ci, vp]),
+    "rpnet_seg_tally": (ci, [C.POINTER(vp), C.POINTER(C.c_int32), ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "rpnet_argmax_masks": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
     "rpnet_align_labels": (ci, [vp, vp, vp, cs, vp]),
     "rpnet_debug_lds_canary": (ci, [ci, ci, C.c_longlong, vp, vp]),
@@ -129,7 +130,7 @@ _SIGS = {
     "rpnet_debug_mfma_spin": (ci, [ci, ci, C.c_longlong, vp, vp]),
 }
 ABI_SYMBOLS = tuple(_SIGS)
-ABI_VERSION = 109      # RPNET_ABI_VERSION of include/rpnet_abi.h
+ABI_VERSION = 110      # RPNET_ABI_VERSION of include/rpnet_abi.h
 
 
 def lib_path():

@@ -1,0 +1,172 @@
+"""Segment a whole volume on the device: predicted masks and the Dice tallies of every refinement iteration.
+
+The reference's driver (test_rpnet.py:151-258, restated in tools/eval_driver.py:evaluate) walks a volume in 2-slice calls and, per
+call, runs T + 1 softmax launches, T + 1 index launches and T + 1 blocking `.cpu()` copies, then thresholds and counts in numpy —
+and throws the segmentation away.  `VolumeSegmenter` runs the same model calls (`batch` slices at a time, through
+`rpnet_amd.graph.GraphedEval` where it applies) and follows each with ONE launch (`rpnet_seg_tally`, csrc/segtally.hip) that
+thresholds every refinement iteration's logits, the output and the affine baseline, adds their |P and T|, |P|, |T| to a counter
+table in device memory and writes the predicted mask.  The counters cross to the host once per volume; the mask stays on the
+device until it is asked for.
+"""
+import ctypes as C
+import weakref
+from collections import namedtuple
+
+import torch
+
+from . import hip
+from .graph import GraphedEval
+
+VolumeResult = namedtuple("VolumeResult", ["mask", "counts", "dice"])
+
+# One GraphedEval per net, shared by every VolumeSegmenter of that net.  A captured graph holds the addresses of the net's weight
+# packs, and a second `GraphedEval(net)` clears that cache (graph.py:__init__): the first wrapper's graphs would then replay on
+# freed memory.  One wrapper serves every shape (one graph per shape).
+_GRAPHED = weakref.WeakKeyDictionary()
+
+
+def graphed_eval(net):
+    """the GraphedEval that the VolumeSegmenters of `net` share (made on first use)"""
+    ge = _GRAPHED.get(net)
+    if ge is None:
+        ge = _GRAPHED[net] = GraphedEval(net)
+    return ge
+
+
+def dice_from_counts(counts, decimal=4):
+    """[K-1][3] rows {|P and T|, |P|, |T|} -> per-class Dice 2|P and T| / (|P| + |T|), None for a class absent from the ground
+    truth, rounded as `utils.util.dice_score_seperate` rounds (the numbers the driver prints)."""
+    scores = []
+    for inter, p, t in ((int(r[0]), int(r[1]), int(r[2])) for r in counts):
+        scores.append(round(float(2 * inter / float(t + p)), decimal) if t else None)
+    return scores
+
+
+def seg_tally(sources, kinds, n_valid, labels=None, counts=None, mask=None, mask_src=0, K=None, _table=None):
+    """One `rpnet_seg_tally` launch on the current stream.  sources: fp32 tensors, logits [N,K,H,W] (kind 0) or 0/1 masks [N,H,W]
+    (kind 1); n_valid: int32 device scalar; labels int32 [N,H,W]; counts int64 [S,K-1,3] (accumulated into); mask uint8 [N,H,W]."""
+    first = sources[0]
+    if kinds[0] == 0:
+        N, Kk, H, W = first.shape
+    else:
+        (N, H, W), Kk = first.shape, K
+    K = Kk if K is None else K
+    hip.require_gpu(*sources, labels, counts, mask, n_valid)
+    for t, kind in zip(sources, kinds):
+        want = (N, K, H, W) if kind == 0 else (N, H, W)
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"seg_tally: a source of kind {kind} must be a contiguous fp32 tensor of shape {want}, got {tuple(t.shape)} {t.dtype}")
+    for t, dt, shape, what in ((labels, torch.int32, (N, H, W), "labels"), (mask, torch.uint8, (N, H, W), "mask"),
+                               (counts, torch.int64, (len(sources), K - 1, 3), "counts"), (n_valid, torch.int32, None, "n_valid")):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape)):
+            raise ValueError(f"seg_tally: {what} must be a contiguous {dt} tensor" + (f" of shape {shape}" if shape else ""))
+    S = len(sources)
+    if _table is None:
+        _table = ((C.c_void_p * S)(*[t.data_ptr() for t in sources]), (C.c_int32 * S)(*kinds))
+    hip.call("rpnet_seg_tally", _table[0], _table[1], S, hip.ptr(labels), hip.ptr(n_valid), hip.ptr(counts), hip.ptr(mask),
+             mask_src, N, K, H, W)
+
+
+class VolumeSegmenter:
+    """`VolumeSegmenter(net, batch=8, graphed=True)(support_images, support_fg, query_images, appr_query_labels, query_labels=None)`
+    -> VolumeResult(mask, counts, dice).
+
+    Arguments are the volume-level tensors of a `FewshotRegReader` eval item: nested lists `[way][shot]` of support images
+    [S,1,H,W] and foreground masks [S,H,W] (background = 1 - foreground), query images [S,1,H,W], the approximate (affine) labels
+    [S,H,W] and, optionally, the ground truth [S,H,W].
+      mask    uint8 [S,H,W] on the device: the class predicted by the final output
+      counts  int64 [T+2, K-1, 3] on the host, rows = refinement 0 .. T-1, output, affine baseline; columns |P and T|, |P|, |T|
+      dice    {'fewshot': [..], 'affine': [..], 'refinement': {i: [..]}} per class, as the driver prints them
+    (counts and dice are None without query_labels.)  The slices go through the model `batch` at a time in eval mode under
+    no_grad; the last batch is filled by repeating the last slice, and the device scalar `n_valid` keeps the filler out of the
+    tallies and the mask.  graphed and 1-way 1-shot: the calls go through GraphedEval — `graphed=True`: the one wrapper all
+    VolumeSegmenters of this net share (`graphed_eval(net)`), or pass your own `GraphedEval(net)` to use that; a net must not get a
+    second wrapper while graphs of the first are in use (graph.py clears the net's weight packs) — otherwise eager `net(...)`.  The
+    only device-to-host transfer this class adds is the counter table, once per volume."""
+
+    def __init__(self, net, batch=8, graphed=True):
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        self.net, self.batch, self.graphed = net.eval(), int(batch), bool(graphed)
+        self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
+        if self._graphed_eval is not None and self._graphed_eval.net is not net:
+            raise ValueError("VolumeSegmenter: the GraphedEval handed in wraps another net")
+        self._tables = {}       # id(static output dict of a captured shape) -> (pointer array, kinds): built once per captured shape
+        self._nv = None
+
+    def _model(self, n_ways, n_shots):
+        if not (self.graphed and n_ways == 1 and n_shots == 1):
+            return self.net
+        if self._graphed_eval is None:
+            self._graphed_eval = graphed_eval(self.net)
+        return self._graphed_eval
+
+    def _table(self, out, appr, shape):
+        """host arrays of the launch's sources: refinement 0 .. T-1, output, affine baseline.  For the static outputs of a captured
+        graph the arrays are kept (only the baseline's pointer moves with the batch); outputs of an eager call are fresh tensors."""
+        ge = self._graphed_eval
+        entry = ge._graphs.get(shape) if ge is not None else None
+        static = entry is not None and entry[2] is out
+        tab = self._tables.get(id(out)) if static else None
+        if tab is None:
+            T = len(out["refinement"])
+            srcs = [out["refinement"][i] for i in range(T)] + [out["output"]]
+            for t in srcs:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise RuntimeError("VolumeSegmenter: the model's logits must be contiguous fp32 tensors")
+            S = len(srcs) + 1
+            tab = ((C.c_void_p * S)(*([t.data_ptr() for t in srcs] + [0])), (C.c_int32 * S)(*([0] * (S - 1) + [1])), srcs)
+            if static:
+                self._tables[id(out)] = tab
+        tab[0][len(tab[2])] = appr.data_ptr()
+        return tab
+
+    def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None):
+        dev = next(self.net.parameters()).device
+        n_ways, n_shots = len(support_images), len(support_images[0])
+        S, B = query_images.shape[0], self.batch
+        H, W = query_images.shape[-2:]
+        K = n_ways + 1
+        nb = -(-S // B)
+        pad = nb * B - S
+
+        def prep(x, dtype=torch.float32):
+            x = x.to(device=dev, dtype=dtype)
+            if pad:
+                x = torch.cat([x, x[-1:].expand(pad, *x.shape[1:])], 0)       # the filler of the last batch: the last slice again
+            return x.contiguous()
+
+        with torch.no_grad():
+            si = [[prep(x) for x in way] for way in support_images]
+            fg = [[prep(x) for x in way] for way in support_fg]
+            bg = [[1 - x for x in way] for way in fg]
+            qi, appr = prep(query_images), prep(appr_query_labels)
+            labels = prep(query_labels, torch.int32) if query_labels is not None else None
+            mask = torch.empty((nb * B, H, W), device=dev, dtype=torch.uint8)
+            if self._nv is None or self._nv.device != dev:
+                self._nv = torch.empty(1, device=dev, dtype=torch.int32)
+            model = self._model(n_ways, n_shots)
+            counts, nv_now = None, None
+            for i in range(nb):
+                sl = slice(i * B, (i + 1) * B)
+                out = model([[x[sl] for x in way] for way in si], [[x[sl] for x in way] for way in fg],
+                            [[x[sl] for x in way] for way in bg], [qi[sl]], appr_query_labels=appr[sl])
+                # (which tensors hold this call's logits is known only now: GraphedEval returns its static outputs after a replay,
+                # fresh ones when it had to redo the call eagerly on measured fp16 scales)
+                tab = self._table(out, appr[sl], tuple(si[0][0][sl].shape))
+                T = len(tab[2]) - 1
+                if labels is not None and counts is None:
+                    counts = torch.zeros((T + 2, K - 1, 3), device=dev, dtype=torch.int64)
+                n_valid = min(B, S - i * B)
+                if n_valid != nv_now:
+                    self._nv.fill_(n_valid)
+                    nv_now = n_valid
+                seg_tally(tab[2] + [appr[sl]], [0] * (T + 1) + [1], self._nv, labels[sl] if labels is not None else None, counts,
+                          mask[sl], mask_src=T, K=K, _table=tab)
+        if counts is None:
+            return VolumeResult(mask[:S], None, None)
+        host = counts.cpu().numpy()                 # the one transfer of the volume
+        T = host.shape[0] - 2
+        dice = {"fewshot": dice_from_counts(host[T]), "affine": dice_from_counts(host[T + 1]),
+                "refinement": {i: dice_from_counts(host[i]) for i in range(T)}}
+        return VolumeResult(mask[:S], host, dice)

@@ -4,7 +4,11 @@
 iteration), using only the symbols that driver imports, at the reference's import paths.
 The reference file itself cannot run offline (it needs tensorboard and the private data).
 
-    python tools/eval_driver.py --yaml yamls/example.yml [--items 2]
+    python tools/eval_driver.py --yaml yamls/example.yml [--items 2] [--on-device] [--batch 8] [--save-pred DIR]
+
+--on-device: the same lines from rpnet_amd.volume.VolumeSegmenter (masks and Dice tallies on the device, one transfer per volume,
+`--batch` slices per model call through the captured graph); --save-pred DIR writes each volume's predicted mask as
+DIR/<pid>_<class>.nrrd (uint8, gzip) and implies --on-device.
 """
 import argparse
 import os
@@ -61,10 +65,46 @@ def evaluate(net, loader, config, n_items=None, batch_size=2):
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
+def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None):
+    """`evaluate` through rpnet_amd.volume.VolumeSegmenter: the same printed lines and return value; thresholds, Dice tallies and the
+    predicted mask are formed on the device, the tallies cross to the host once per volume.  save_pred: a directory that receives
+    every volume's mask as <pid>_<class>.nrrd; segmenter: a VolumeSegmenter to reuse (its captured graphs live with it)."""
+    from rpnet_amd.utils import nrrd
+    from rpnet_amd.volume import VolumeSegmenter
+    seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed)
+    classes = config["eval_classes"]
+    dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
+    if save_pred:
+        os.makedirs(save_pred, exist_ok=True)
+    for j in range(len(loader) if n_items is None else min(n_items, len(loader))):
+        s = loader[j]
+        res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"])
+        name = classes[s["class_id"]]
+        d_aff, d_few = res.dice["affine"][0], res.dice["fewshot"][0]
+        with torch.no_grad():
+            ncc = NCC(s["query_images"].float().cuda(), s["warped_supp"].unsqueeze(1).cuda()).item()
+        dsc_affine[name].append(d_aff)
+        dsc_fewshot[name].append(d_few)
+        line = f"{j} {s['pid']} affine ({ncc:.4f}) {d_aff}, fewshot {d_few}"
+        for k, d in res.dice["refinement"].items():
+            dsc_ref[name][k].append(d[0])
+            line += f" ref {k} {d[0]},"
+        print(line)
+        if save_pred:
+            nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), res.mask.cpu().numpy(), encoding="gzip")
+    for name in classes:
+        if dsc_fewshot[name]:
+            print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}")
+    return dsc_affine, dsc_fewshot, dsc_ref
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--yaml", default="yamls/example.yml")
     ap.add_argument("--items", type=int, default=None)
+    ap.add_argument("--on-device", action="store_true", help="masks and Dice tallies on the device (rpnet_amd.volume.VolumeSegmenter)")
+    ap.add_argument("--batch", type=int, default=None, help="slices per model call (default: 2, or 8 with --on-device)")
+    ap.add_argument("--save-pred", default=None, metavar="DIR", help="write each volume's mask as DIR/<pid>_<class>.nrrd; implies --on-device")
     a = ap.parse_args()
     config, args = load_yaml(a.yaml)
     config["n_iter_refinement"] = config["n_test_iter_refinement"]            # test_rpnet.py:51
@@ -75,7 +115,10 @@ def main():
         state = net.state_dict()
         state.update(torch.load(args.ckpt)["state_dict"])
         net.load_state_dict(state)
-    evaluate(net, loader, config, a.items)
+    if a.on_device or a.save_pred:
+        evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred)
+    else:
+        evaluate(net, loader, config, a.items, a.batch or 2)
 
 
 if __name__ == "__main__":
