@@ -52,8 +52,9 @@ enum rpnet_status {
  * later are optional features that are off at zero) and SHOULD compare rpnet_version() with the RPNET_ABI_VERSION it was built
  * against.  109: rpnet_bn_eval_relu, rpnet_bn_eval_bwd, rpnet_conv1_dgrad_bn added (the gradient through eval-mode BatchNorm and the
  * input images' gradient); nothing existing changed.  110: rpnet_seg_tally added (masks and Dice tallies of an evaluation call);
- * nothing existing changed. */
-#define RPNET_ABI_VERSION 110
+ * nothing existing changed.  111: rpnet_slice_minmax, rpnet_augment_affine, rpnet_elastic_field, rpnet_elastic_apply added (train-time
+ * augmentation of episode slices); nothing existing changed. */
+#define RPNET_ABI_VERSION 111
 int rpnet_version(void);
 const char* rpnet_last_error_string(void);
 
@@ -643,6 +644,35 @@ int rpnet_demons_register(const float* moving, const float* fixed, const float* 
                           void* workspace, size_t workspace_bytes, rpnet_stream_t stream);
 int rpnet_displacement_warp(const float* x, const float* disp, float* out, int S, int H, int W, float threshold, float scale,
                             float shift, rpnet_stream_t stream);
+
+/* ------------------------------------------------- train-time augmentation of episode slices (csrc/augment.hip)
+ * What the train-mode reader does to the query slices on the host (rpnet_amd/utils/volume_reader.py, after
+ * dataset/few_shot_reader.py:27-61,200-210 and brain_reader.py:208-294), for all S slices [S][H][W] of a call in one launch
+ * per stage.  Inputs and outputs never alias (gathers).  S == 0: success, nothing launched.  S <= 65535, S*H*W < 2^31.
+ * rpnet_slice_minmax    mm [S][2] = {min, max} of each slice.
+ * rpnet_augment_affine  gamma_transform (where the slice's flag is set) then random_transform: params [S][8] = the 2x3 inverse
+ *                       map about the image centre in pixels (m00 m01 m02 m10 m11 m12), gamma, gamma flag (0 / non-zero), in
+ *                       DEVICE memory; mm from rpnet_slice_minmax on `img`.  img in [-1,1] -> [0,1] -> power law with the slice's
+ *                       min / max -> nearest sampling (grid_sample nearest, align_corners=False, zeros outside, half to even) ->
+ *                       exact zeros take `lo`, the minimum of the [0,1] image before sampling -> [-1,1].  lab: the same sampling.
+ *                       Either pair (img, img_out) / (lab, lab_out) may be NULL: with labels alone this is
+ *                       random_label_transform and mm may be NULL.
+ * rpnet_elastic_field   field [2][H][W] fp32 = alpha * scipy.ndimage.gaussian_filter(noise [2][H][W] fp64) with the normalised
+ *                       weights [2*radius+1] (fp64, device memory), separable, mode reflect (period 2n: any radius), sums in fp64;
+ *                       tmp [2][H][W] fp64.  Two launches.
+ * rpnet_elastic_apply   elastic_transform_all for S slices sharing minv (HOST pointer to the 2x3 fp64 inverse affine, x' = m00 x +
+ *                       m01 y + m02, read before the call returns) and field = (dx, dy): stage 1 image bilinear at Minv p / mask
+ *                       nearest at rint(Minv p) into img_tmp / mask_tmp, stage 2 image bilinear / mask nearest (floor(c + 0.5))
+ *                       at (y + dy, x + dx) of THAT result.  scipy's mode "constant": a coordinate outside [0, n-1] on either axis
+ *                       gives padding_value (image) or 0 (mask), without blending.  Coordinates and weights in fp64.  Either
+ *                       triple (img, img_tmp, img_out) / (mask, mask_tmp, mask_out) may be NULL.  Two launches. */
+int rpnet_slice_minmax(const float* x, float* mm, int S, int H, int W, rpnet_stream_t stream);
+int rpnet_augment_affine(const float* img, const float* lab, const float* params, const float* mm, float* img_out, float* lab_out,
+                         int S, int H, int W, rpnet_stream_t stream);
+int rpnet_elastic_field(const double* noise, const double* weights, int radius, double alpha, double* tmp, float* field, int H, int W,
+                        rpnet_stream_t stream);
+int rpnet_elastic_apply(const float* img, const float* mask, const double* minv, const float* field, float* img_tmp, float* mask_tmp,
+                        float* img_out, float* mask_out, int S, int H, int W, float padding_value, rpnet_stream_t stream);
 
 #ifdef __cplusplus
 }

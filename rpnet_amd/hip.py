@@ -125,12 +125,16 @@ _SIGS = {
     "rpnet_seg_tally": (ci, [C.POINTER(vp), C.POINTER(C.c_int32), ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "rpnet_argmax_masks": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
     "rpnet_align_labels": (ci, [vp, vp, vp, cs, vp]),
+    "rpnet_slice_minmax": (ci, [vp, vp, ci, ci, ci, vp]),
+    "rpnet_augment_affine": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
+    "rpnet_elastic_field": (ci, [vp, vp, ci, cd, vp, vp, ci, ci, vp]),
+    "rpnet_elastic_apply": (ci, [vp, vp, C.POINTER(cd), vp, vp, vp, vp, vp, ci, ci, ci, cf, vp]),
     "rpnet_debug_lds_canary": (ci, [ci, ci, C.c_longlong, vp, vp]),
     "rpnet_debug_fastdiv_selftest": (C.c_longlong, [ci]),
     "rpnet_debug_mfma_spin": (ci, [ci, ci, C.c_longlong, vp, vp]),
 }
 ABI_SYMBOLS = tuple(_SIGS)
-ABI_VERSION = 110      # RPNET_ABI_VERSION of include/rpnet_abi.h
+ABI_VERSION = 111     # RPNET_ABI_VERSION of include/rpnet_abi.h
 
 
 def lib_path():

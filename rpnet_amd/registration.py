@@ -9,6 +9,8 @@ The reference does this slice by slice with ~20 small torch operators per Adam s
 configuration (few_shot_reader.py:135-143) — and it dominates the wall-clock of real evaluation outside the
 model.  No CPU fallback: the oracle (oracle/registration_oracle.py) is test infrastructure.
 """
+import functools
+
 import torch
 
 from . import hip
@@ -17,9 +19,11 @@ from .hip import call, ptr
 ADAM = dict(lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8)     # torch.optim.Adam defaults, lr of few_shot_reader.py:147
 
 
+@functools.lru_cache(maxsize=64)
 def base_grid(n, device):
     """the 1-D base grid of F.affine_grid(align_corners=False), from the function the reference itself calls
-    (so that coordinates that sit exactly on pixel centres round the same way, csrc/registration.hip)"""
+    (so that coordinates that sit exactly on pixel centres round the same way, csrc/registration.hip).  Cached per
+    (n, device): read-only, and a call after the first makes no host-to-device copy."""
     return (torch.linspace(-1, 1, n) * (n - 1) / n).to(device)
 
 
@@ -50,6 +54,11 @@ def identity_grid_warp(x, threshold=-1.0, scale=1.0, shift=0.0):
     return out
 
 
+@functools.lru_cache(maxsize=16)
+def _device_kernel(sigma, device):
+    return gaussian_kernel_2d(sigma).to(device)
+
+
 def gaussian_kernel_2d(sigma=(2.0, 2.0)):
     """the smoothing kernel of GaussianRegulariser (net/registration.py:14-49,106-135): normalised 1-D Gaussians of
     2 ceil(2 sigma) + 1 taps, their outer product renormalised, in fp32"""
@@ -69,10 +78,9 @@ def demons_register(moving, fixed, iters=50, sigma=(2.0, 2.0)):
     final flow, NCC [S] at the last evaluated flow)."""
     hip.require_gpu(moving, fixed)
     S, H, W = moving.shape
-    kern = gaussian_kernel_2d(sigma)
+    kern = _device_kernel(tuple(sigma), moving.device)
     if kern.shape[0] != kern.shape[1]:
         raise NotImplementedError("anisotropic smoothing kernel sizes")
-    kern = kern.to(moving.device)
     flow = torch.empty((S, 2, H, W), device=moving.device, dtype=torch.float32)
     disp, loss = torch.empty_like(flow), torch.empty((S,), device=moving.device, dtype=torch.float32)
     wb = hip.query("rpnet_demons_workspace_bytes", S, H, W)
@@ -89,28 +97,38 @@ def displacement_warp(x, disp, threshold=-1.0, scale=1.0, shift=0.0):
     return out
 
 
+def register_slices(src, dst, lab, do_deformable=True):
+    """The registration pre-step on device tensors: src (support), dst (query) [S,H,W] in [0,1], lab [S,H,W], float32 on
+    the GPU -> (field, reg_pred [S,H,W], warped_src [S,H,W], affine_reg_pred [S,H,W], affine_warped_src [S,H,W]), all
+    on the GPU, nothing copied to the host; field = theta [S,2,3], or (theta, flow [S,2,H,W]) with do_deformable."""
+    theta, _ = affine_register(src, dst)
+    aw_lab, aw_src = affine_warp(lab, theta), affine_warp(src, theta)
+    if do_deformable:
+        # few_shot_reader.py:135-143,152-161: 50 demons steps on the affine-warped source (net/registration.py:489-502)
+        flow, disp, _ = demons_register(aw_src, dst)
+        field = (theta, flow)
+        reg_pred = displacement_warp(aw_lab, disp, threshold=0.1)
+        warped_src = displacement_warp(aw_src, disp, scale=2.0, shift=-1.0)
+    else:
+        field = theta
+        reg_pred = identity_grid_warp(aw_lab, threshold=0.1)
+        warped_src = identity_grid_warp(aw_src, scale=2.0, shift=-1.0)
+    affine_reg_pred = affine_warp(lab, theta, threshold=0.1)
+    affine_warped_src = affine_warp(src, theta, scale=2.0, shift=-1.0)
+    return field, reg_pred, warped_src, affine_reg_pred, affine_warped_src
+
+
 def get_registration_field(query_images, support_images, support_labels, do_deformable=True, device="cuda:0"):
     """Signature and return tuple of dataset/few_shot_reader.py:109 (registration_field, py_reg_pred,
     warped_src_list, py_affine_reg_pred, affine_warped_src_list).  query_images [S,1,H,W] in [-1,1];
     support_images [[ [S,1,H,W] ]]; support_labels [[ [S,H,W] ]].  `registration_field` holds the per-slice affine
     matrices [S,2,3] — with do_deformable=True the pair (thetas, flows [S,2,H,W]) — where the reference returns
     [module, grid] pairs that nothing downstream reads (RP_Net.forward ignores its registration_field argument,
-    net/rp_net.py:226).  Outputs are CPU tensors / numpy arrays like the reference's."""
+    net/rp_net.py:226).  Outputs are CPU tensors / numpy arrays like the reference's (register_slices: the same
+    launches without the copies)."""
     src = ((support_images[0][0][:, 0].float() + 1) / 2.0).to(device)
     dst = ((query_images[:, 0].float() + 1) / 2.0).to(device)
     lab = support_labels[0][0].float().to(device)
-    theta, _ = affine_register(src, dst)
-    aw_lab, aw_src = affine_warp(lab, theta), affine_warp(src, theta)
-    if do_deformable:
-        # few_shot_reader.py:135-143,152-161: 50 demons steps on the affine-warped source (net/registration.py:489-502)
-        flow, disp, _ = demons_register(aw_src, dst)
-        py_reg_pred = displacement_warp(aw_lab, disp, threshold=0.1)[:, None].cpu()
-        warped_src = displacement_warp(aw_src, disp, scale=2.0, shift=-1.0).cpu().numpy()
-        py_affine_reg_pred = affine_warp(lab, theta, threshold=0.1)[:, None].cpu()
-        affine_warped_src = affine_warp(src, theta, scale=2.0, shift=-1.0).cpu().numpy()
-        return (theta.cpu(), flow.cpu()), py_reg_pred, warped_src, py_affine_reg_pred, affine_warped_src
-    py_reg_pred = identity_grid_warp(aw_lab, threshold=0.1)[:, None].cpu()
-    warped_src = identity_grid_warp(aw_src, scale=2.0, shift=-1.0).cpu().numpy()
-    py_affine_reg_pred = affine_warp(lab, theta, threshold=0.1)[:, None].cpu()
-    affine_warped_src = affine_warp(src, theta, scale=2.0, shift=-1.0).cpu().numpy()
-    return theta.cpu(), py_reg_pred, warped_src, py_affine_reg_pred, affine_warped_src
+    field, reg_pred, warped_src, aff_pred, aff_src = register_slices(src, dst, lab, do_deformable)
+    field = tuple(f.cpu() for f in field) if do_deformable else field.cpu()
+    return field, reg_pred[:, None].cpu(), warped_src.cpu().numpy(), aff_pred[:, None].cpu(), aff_src.cpu().numpy()

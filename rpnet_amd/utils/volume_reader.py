@@ -22,7 +22,6 @@ their documented behaviour (torchvision's tensor path: inverse affine matrix abo
 third-party packages is UNPINNED (they cannot be imported here); everything else is pinned by
 tests/golden/volume_reader.npz, produced by the reference's own classes (tests/golden/gen_golden_reader.py).
 """
-import math
 import os
 import random
 
@@ -31,6 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from . import nrrd
+from ..augment import LABEL_TRANSFORM_ARGS, TRANSFORM_ARGS, draw_elastic, draw_gamma, draw_random_affine
 
 
 # --------------------------------------------------------------------------------------------------- array helpers
@@ -99,15 +99,19 @@ def compute_grid(img_size):
 
 
 # --------------------------------------------------------------------------------------------------- augmentations
-def gamma_transform(img, gamma_range):
-    """few_shot_reader.py:200-210 (`gamma_tansform`): a random power law on the [0,1]-mapped slice, one
-    np.random.rand() draw"""
+def gamma_apply(img, gamma):
+    """the power law of gamma_transform with a given exponent"""
     img = (img + 1) / 2.0
-    gamma = np.random.rand() * (gamma_range[1] - gamma_range[0]) + gamma_range[0]
     lo = img.min()
     span = img.max() - lo + 1e-5
     img = span * np.power((img - lo + 1e-5) * 1.0 / span, gamma) + lo
     return img * 2 - 1
+
+
+def gamma_transform(img, gamma_range):
+    """few_shot_reader.py:200-210 (`gamma_tansform`): a random power law on the [0,1]-mapped slice, one
+    np.random.rand() draw"""
+    return gamma_apply(img, draw_gamma(gamma_range))
 
 
 gamma_tansform = gamma_transform          # the reference's spelling
@@ -121,34 +125,10 @@ def gamma_transform_with_label(img, label, gamma_range):
 gamma_tansform_with_label = gamma_transform_with_label
 
 
-def _uniform(lo, hi):
-    return float(torch.empty(1).uniform_(float(lo), float(hi)).item())
-
-
-def random_affine(x, degrees, translate=None, scale=None, shear=None):
-    """torchvision.transforms.RandomAffine(degrees, translate, scale, shear) on a [N,C,H,W] tensor, restated from its
-    documentation (UNPINNED, see the module header): angle ~ U(-degrees, degrees); integer shift ~ round(U(-t W, t W));
-    scale ~ U(scale); x-shear ~ U(-shear, shear); output pixel p samples the input at A^-1 p about the image centre,
-    nearest neighbour, zeros outside.  Draw order: angle, tx, ty, scale, shear (torch generator)."""
+def affine_sample(x, m):
+    """[N,C,H,W] sampled through the inverse map `m` (six numbers, about the image centre, in pixels): nearest
+    neighbour, zeros outside (torchvision's tensor path: affine_grid + grid_sample)"""
     H, W = x.shape[-2:]
-    deg = (-degrees, degrees) if np.isscalar(degrees) else degrees
-    angle = _uniform(*deg)
-    tx = ty = 0
-    if translate is not None:
-        tx = int(round(_uniform(-translate[0] * W, translate[0] * W)))
-        ty = int(round(_uniform(-translate[1] * H, translate[1] * H)))
-    s = _uniform(*scale) if scale is not None else 1.0
-    shx = 0.0
-    if shear is not None:
-        sh = (-shear, shear) if np.isscalar(shear) else shear
-        shx = _uniform(sh[0], sh[1])
-    rot, sx = math.radians(angle), math.radians(shx)
-    # forward map = T(translate) R(rot) Shear(sx) S(s) about the centre; rows of its inverse:
-    a, b = math.cos(rot), -math.cos(rot) * math.tan(sx) - math.sin(rot)
-    c, d = math.sin(rot), -math.sin(rot) * math.tan(sx) + math.cos(rot)
-    m = [d / s, -b / s, 0.0, -c / s, a / s, 0.0]
-    m[2] = m[0] * -tx + m[1] * -ty
-    m[5] = m[3] * -tx + m[4] * -ty
     theta = torch.tensor(m, dtype=x.dtype).reshape(1, 2, 3)
     base = torch.empty(1, H, W, 3, dtype=x.dtype)
     base[..., 0] = torch.linspace(-W * 0.5 + 0.5, W * 0.5 - 0.5, W)
@@ -158,44 +138,46 @@ def random_affine(x, degrees, translate=None, scale=None, shear=None):
     return F.grid_sample(x, grid.expand(x.shape[0], -1, -1, -1), mode="nearest", padding_mode="zeros", align_corners=False)
 
 
-def random_transform(images, labels):
-    """few_shot_reader.py:27-48: one RandomAffine(5, translate 0.2, scale 0.7-1.5) for the slice [1,1,H,W] (in [-1,1])
-    and its label [1,H,W]; pixels that come out exactly 0 in the [0,1] image take the slice minimum."""
+def random_affine(x, degrees, translate=None, scale=None, shear=None):
+    """torchvision.transforms.RandomAffine(degrees, translate, scale, shear) on a [N,C,H,W] tensor, restated from its
+    documentation (UNPINNED, see the module header): angle ~ U(-degrees, degrees); integer shift ~ round(U(-t W, t W));
+    scale ~ U(scale); x-shear ~ U(-shear, shear); output pixel p samples the input at A^-1 p about the image centre,
+    nearest neighbour, zeros outside.  Draw order: angle, tx, ty, scale, shear (torch generator; the draws are
+    rpnet_amd.augment.draw_random_affine, shared with the device path)."""
+    H, W = x.shape[-2:]
+    return affine_sample(x, draw_random_affine(H, W, degrees, translate=translate, scale=scale, shear=shear))
+
+
+def transform_apply(images, labels, m):
+    """random_transform with a given inverse map"""
     images = (images + 1) / 2
     lo = images.min()
-    both = random_affine(torch.cat([images, labels[None, ...]], dim=1), 5, translate=(0.2, 0.2), scale=(0.7, 1.5), shear=0)
+    both = affine_sample(torch.cat([images, labels[None, ...]], dim=1), m)
     images, labels = both[:, [0]], both[:, 1]
     images[images == 0] = lo
     return images * 2 - 1, labels
 
 
+def random_transform(images, labels):
+    """few_shot_reader.py:27-48: one RandomAffine(5, translate 0.2, scale 0.7-1.5) for the slice [1,1,H,W] (in [-1,1])
+    and its label [1,H,W]; pixels that come out exactly 0 in the [0,1] image take the slice minimum."""
+    H, W = images.shape[-2:]
+    return transform_apply(images, labels, draw_random_affine(H, W, **TRANSFORM_ARGS))
+
+
 def random_label_transform(labels):
     """few_shot_reader.py:51-61"""
-    return random_affine(labels[None, None, ...], 5, translate=(0.02, 0.02), scale=(0.5, 1.5), shear=5)[:, 0]
+    H, W = labels.shape[-2:]
+    return affine_sample(labels[None, None, ...], draw_random_affine(H, W, **LABEL_TRANSFORM_ARGS))[:, 0]
 
 
-def _three_point_affine(src, dst):
-    """the 2x3 M with M [x, y, 1]^T = dst for three point pairs (cv2.getAffineTransform)"""
-    A = np.concatenate([src, np.ones((3, 1))], axis=1).astype(np.float64)
-    return np.linalg.solve(A, dst.astype(np.float64)).T
-
-
-def elastic_transform_all(image, mask, alpha=1000, sigma=30, alpha_affine=0.04, padding_value=-1.0, random_state=None):
-    """brain_reader.py:208-294: the same in-plane random affine (three corner points jittered by +-alpha_affine) and
-    elastic displacement (Gaussian-smoothed uniform noise, sigma, times alpha) for every slice of image [1,D,H,W]
-    and mask [num_class,D,H,W]; image bilinear with `padding_value` outside, mask nearest with 0 outside.  UNPINNED
-    (cv2 absent; the reference draws from an unseeded RandomState)."""
+def elastic_apply(image, mask, Minv, noise, alpha=1000, sigma=30, padding_value=-1.0):
+    """elastic_transform_all with given draws: Minv the 2x3 inverse affine, noise [2,H,W] the uniform planes (x first)"""
     from scipy.ndimage import gaussian_filter, map_coordinates
-    rs = random_state if random_state is not None else np.random.RandomState(None)
     plane = image.shape[2:]
     n_cls, D, Hh, Ww = mask.shape
-    centre, half = np.float32(plane) // 2, min(plane) // 3
-    pts1 = np.float32([centre + half, [centre[0] + half, centre[1] - half], centre - half])
-    pts2 = pts1 + rs.uniform(-alpha_affine, alpha_affine, size=pts1.shape).astype(np.float32)
-    M = _three_point_affine(pts1, pts2)
-    Minv = np.linalg.inv(np.vstack([M, [0, 0, 1]]))[:2]
-    dx = gaussian_filter(rs.rand(*plane) * 2 - 1, sigma) * alpha
-    dy = gaussian_filter(rs.rand(*plane) * 2 - 1, sigma) * alpha
+    dx = gaussian_filter(noise[0], sigma) * alpha
+    dy = gaussian_filter(noise[1], sigma) * alpha
     xx, yy = np.meshgrid(np.arange(Ww), np.arange(Hh))
     src_x = Minv[0, 0] * xx + Minv[0, 1] * yy + Minv[0, 2]        # warpAffine: dst(x, y) = src(M^-1 (x, y))
     src_y = Minv[1, 0] * xx + Minv[1, 1] * yy + Minv[1, 2]
@@ -209,6 +191,15 @@ def elastic_transform_all(image, mask, alpha=1000, sigma=30, alpha_affine=0.04, 
                 aff = map_coordinates(mask[j, z], (np.rint(src_y), np.rint(src_x)), order=0, mode="constant", cval=0)
                 new_mask[j, z] = map_coordinates(aff, warp_to, order=0, mode="constant").reshape(plane)
     return new_img, new_mask
+
+
+def elastic_transform_all(image, mask, alpha=1000, sigma=30, alpha_affine=0.04, padding_value=-1.0, random_state=None):
+    """brain_reader.py:208-294: the same in-plane random affine (three corner points jittered by +-alpha_affine) and
+    elastic displacement (Gaussian-smoothed uniform noise, sigma, times alpha) for every slice of image [1,D,H,W]
+    and mask [num_class,D,H,W]; image bilinear with `padding_value` outside, mask nearest with 0 outside.  UNPINNED
+    (cv2 absent; the reference draws from an unseeded RandomState)."""
+    Minv, noise = draw_elastic(image.shape[2:], alpha_affine, random_state)
+    return elastic_apply(image, mask, Minv, noise, alpha, sigma, padding_value)
 
 
 # ----------------------------------------------------------------------------------------------------------- readers

@@ -5,11 +5,14 @@ The reference has NO train script (README "Train" section is empty, SURVEY.md §
 follows the hyper-parameters its yaml carries (yamls/example.yml:64-67,105-116: Adam, init_lr 1e-5,
 weight_decay 1e-4, StepLR every `scheduler_step` epochs, n_iter_refinement = 4, loss dice_ce,
 align_loss_scaler) and writes checkpoints in the format test_rpnet.py loads
-(`{'epoch', 'state_dict'}`, test_rpnet.py:86-94).  Episodes come from the synthetic reader unless
-real data is wired in (§8f.4).  One process per GPU; gradients are exchanged through the flat
+(`{'epoch', 'state_dict'}`, test_rpnet.py:86-94).  Episodes come from the synthetic reader; with
+--data_dir / --set_name they come from NRRD volumes, augmented, registered and cut into batches on the
+device (rpnet_amd/episodes.py, the train-mode FewshotRegReader item without its host round trips).
+One process per GPU; gradients are exchanged through the flat
 bucket (RCCL all-reduce); BatchNorm statistics stay per rank like the reference (no SyncBN).
 
     python train_rpnet.py --yaml yamls/example.yml --steps 100
+    python train_rpnet.py --yaml yamls/example.yml --steps 100 --data_dir data/preprocessed --set_name split/abd_110_train.csv
     tools/launch_ddp.sh 8 train --steps 100        (= python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 ...)
 """
 import argparse
@@ -49,7 +52,10 @@ def episode(seed, batch, size, dev):
             [t(ep["query_images"])], t(ep["query_labels"]), t(ep["appr_query_labels"]))
 
 
-def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, seed=0, steps_per_epoch=50, n_ways=1, n_shots=1):
+def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, seed=0, steps_per_epoch=50, n_ways=1, n_shots=1,
+          source=None):
+    """source: a rpnet_amd.episodes.DeviceEpisodeSource; its batch(batch) replaces the synthetic episodes (`size` is then
+    whatever the volumes' crop_size gives)"""
     rank = dist.get_rank() if dist.is_initialized() else 0
     net = model_factory[config.get("net", "RP_Net")](pretrained_path=config.get("pretrained_path"),
                                                     cfg={"align": True, "backbone": config.get("backbone", "UNet")},
@@ -72,7 +78,7 @@ def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, 
     import concurrent.futures
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=4)
     gen = lambda k: pool.submit(make_episode, seed + 1000 * rank + k, batch, size, n_shots=n_shots, n_ways=n_ways)  # noqa: E731
-    pending = [gen(k) for k in range(min(4, steps))]
+    pending = [gen(k) for k in range(min(4, steps))] if source is None else []
 
     def to_dev(ep):
         t = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)  # noqa: E731
@@ -81,9 +87,12 @@ def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, 
                 t(ep["appr_query_labels"]))
 
     for it in range(steps):
-        si, fg, bg, qi, ql, appr = to_dev(pending.pop(0).result())
-        if it + 4 < steps:
-            pending.append(gen(it + 4))
+        if source is not None:
+            si, fg, bg, qi, ql, appr = source.batch(batch)       # device tensors, enqueued on this stream: no host wait
+        else:
+            si, fg, bg, qi, ql, appr = to_dev(pending.pop(0).result())
+            if it + 4 < steps:
+                pending.append(gen(it + 4))
         bucket.zero()                       # gradients live in the flat bucket: one memset instead of zero_grad
         out = net(si, fg, bg, qi, appr_query_labels=appr)
         loss = objective(out, ql, scaler)
@@ -115,7 +124,12 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--lr", type=float, default=None)
     ap.add_argument("--out_dir", default=None)
+    ap.add_argument("--data_dir", default=None, help="directory of <pid>_clean.nrrd / <pid>_<roi>.nrrd volumes: train on them "
+                    "(episodes assembled on the device) instead of synthetic episodes; needs --set_name")
+    ap.add_argument("--set_name", default=None, help=".csv / .npy list of the training pids (with --data_dir)")
     a = ap.parse_args()
+    if (a.data_dir is None) != (a.set_name is None):
+        ap.error("--data_dir and --set_name come together")
     config, _ = load_yaml(a.yaml)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     n_dev = torch.cuda.device_count()
@@ -137,7 +151,12 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group(backend)
-    train(config, a.steps, a.batch or config["batch_size"], a.size, dev, lr=a.lr, out_dir=a.out_dir or config.get("out_dir"))
+    source = None
+    if a.data_dir is not None:
+        from rpnet_amd.episodes import DeviceEpisodeSource
+        source = DeviceEpisodeSource(a.data_dir, a.set_name, config, dev, rank=int(os.environ.get("RANK", "0")), world=world)
+    train(config, a.steps, a.batch or config["batch_size"], a.size, dev, lr=a.lr, out_dir=a.out_dir or config.get("out_dir"),
+          source=source)
     if world > 1:
         dist.destroy_process_group()
 
