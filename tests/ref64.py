@@ -1,0 +1,229 @@
+"""Plain float64 references of the small operations around the convolutions (matcher, loss, pooling), one function per
+operation: stock torch operators on the CPU, restated from the reference's operator sequence (net/rp_net.py, net/unet.py,
+net/vgg.py), every backward through autograd.  Test infrastructure only: nothing here imports the package under test, and
+nothing is built from oracle/rpnet_oracle.py (tests/test_host_ref64.py compares the two).
+
+Layouts are the kernels' own: feature maps NHWC ([B, h, w, C] or [B, hw, C]), logits / predictions NCHW, masks
+[nmask, B, H, W].  Every function takes `dtype`: float64 is the reference, float32 the yardstick — the same operators at the
+kernels' precision, whose distance from the float64 result says what fp32 round-off costs on these inputs."""
+import torch
+import torch.nn.functional as F
+
+F64 = torch.float64
+
+
+def _c(t, dtype):
+    return None if t is None else torch.as_tensor(t).detach().cpu().to(dtype)
+
+
+def _nchw(f, h, w):
+    """[B, h*w, C] or [B, h, w, C] -> [B, C, h, w]"""
+    B, C = f.shape[0], f.shape[-1]
+    return f.reshape(B, h, w, C).permute(0, 3, 1, 2)
+
+
+def _nhwc(x):
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
+# ------------------------------------------------------------------------- cosine match (calDist, net/rp_net.py:353-363)
+def _cosine(f, proto, scaler):
+    # f [B, hw, C], proto [B, K, C]: cosine_similarity over the channel axis of [B, 1, C, hw] against [B, K, C, 1]
+    return F.cosine_similarity(f.transpose(1, 2)[:, None], proto[..., None], dim=2, eps=1e-8) * scaler
+
+
+def cosine_match(f, proto, scaler=20.0, dtype=F64):
+    """f [B, hw, C], proto [B, K, C] -> pred [B, K, hw]"""
+    return _cosine(_c(f, dtype), _c(proto, dtype), scaler)
+
+
+def cosine_match_bwd(f, proto, dpred, scaler=20.0, dtype=F64):
+    """-> (df [B, hw, C], dproto [B, K, C])"""
+    f, proto = _c(f, dtype).requires_grad_(True), _c(proto, dtype).requires_grad_(True)
+    return torch.autograd.grad(_cosine(f, proto, scaler), (f, proto), _c(dpred, dtype))
+
+
+# ---------------------------------------------------------------------- bilinear (F.interpolate, net/rp_net.py:303,337)
+def bilinear_up(x, H, W, dtype=F64):
+    """x [planes, h, w] -> [planes, H, W]"""
+    return F.interpolate(_c(x, dtype)[None], size=(H, W), mode="bilinear")[0]
+
+
+def bilinear_up_bwd(dout, h, w, dtype=F64):
+    """dout [planes, H, W] -> din [planes, h, w]"""
+    dout = _c(dout, dtype)
+    x = torch.zeros(dout.shape[0], h, w, dtype=dtype, requires_grad=True)
+    (g,) = torch.autograd.grad(F.interpolate(x[None], size=dout.shape[-2:], mode="bilinear")[0], x, dout)
+    return g
+
+
+# --------------------------------------------------------------- masked pooling (getFeatures, net/rp_net.py:366-376)
+def mask_adjoint(masks, h, w, dtype=F64):
+    """masks [nmask, B, H, W] -> (am [B, nmask, h*w] = U^T mask, msum [B, nmask]); U^T through autograd of the up-sampler"""
+    m = _c(masks, dtype)
+    nmask, B, H, W = m.shape
+    x = torch.zeros(nmask * B, h, w, dtype=dtype, requires_grad=True)
+    (am,) = torch.autograd.grad(F.interpolate(x[None], size=(H, W), mode="bilinear")[0], x, m.reshape(nmask * B, H, W))
+    return am.reshape(nmask, B, h * w).transpose(0, 1).contiguous(), m.sum(dim=(2, 3)).t().contiguous()
+
+
+def _masked_pool(f, m, h, w):
+    up = F.interpolate(_nchw(f, h, w), size=m.shape[-2:], mode="bilinear")          # [B, C, H, W]
+    rows = [torch.sum(up * m[k][:, None], dim=(2, 3)) / (m[k][:, None].sum(dim=(2, 3)) + 1e-5) for k in range(m.shape[0])]
+    return torch.stack(rows, 1)                                                     # [B, nmask, C]
+
+
+def masked_pool(f, masks, h, w, dtype=F64):
+    """the as-written form: interpolate the features up, multiply, sum, divide.  f [B, h*w, C] -> proto [B, nmask, C]"""
+    return _masked_pool(_c(f, dtype), _c(masks, dtype), h, w)
+
+
+def masked_pool_bwd(f, masks, h, w, dproto, dtype=F64):
+    """-> df [B, h*w, C]"""
+    f = _c(f, dtype).requires_grad_(True)
+    (g,) = torch.autograd.grad(_masked_pool(f, _c(masks, dtype), h, w), f, _c(dproto, dtype))
+    return g
+
+
+# -------------------------------------------------- softmax / threshold / pool (net/rp_net.py:269-272,308-311)
+def _softmax_pool(logits, scale, soft):
+    p1 = torch.softmax(logits, dim=1)[:, 1]
+    if not soft:
+        p1 = (p1 > 0.5).to(logits.dtype)
+    return F.avg_pool2d(p1[:, None], scale)[:, 0]
+
+
+def softmax_thresh_pool(logits, scale, soft, dtype=F64):
+    """logits [B, K, H, W] -> mask [B, H/scale, W/scale]"""
+    return _softmax_pool(_c(logits, dtype), scale, soft)
+
+
+def softmax_pool_bwd(logits, dmask, scale, dtype=F64):
+    logits = _c(logits, dtype).requires_grad_(True)
+    (g,) = torch.autograd.grad(_softmax_pool(logits, scale, True), logits, _c(dmask, dtype))
+    return g
+
+
+def mask_avgpool(mask, scale, dtype=F64):
+    """[B, H, W] -> [B, H/scale, W/scale]"""
+    return F.avg_pool2d(_c(mask, dtype)[:, None], scale)[:, 0]
+
+
+# ----------------------------------------------------------------------------- loss (net/rp_net.py:87-127,438,349)
+def dice_loss_softmax(logits, true, eps=1e-7):
+    """the num_classes > 1 branch of the reference's dice_loss_softmax"""
+    K = logits.shape[1]
+    one_hot = torch.eye(K, dtype=logits.dtype)[true].permute(0, 3, 1, 2)
+    probas = torch.softmax(logits, dim=1)
+    dims = (0, 2, 3)
+    inter = torch.sum(probas * one_hot, dims)
+    card = torch.sum(probas + one_hot, dims)
+    return 1 - (2.0 * inter / (card + eps)).mean()
+
+
+def _dice_ce(logits, labels, with_dice, ignore_index, per_sample, sample_weight):
+    B = logits.shape[0]
+    ign = ignore_index if ignore_index >= 0 else -100
+    if per_sample:
+        # alignLoss calls F.cross_entropy(ignore_index=255) once per episode (:438), the caller adds the episodes up and
+        # divides by their number (:343,349); an episode whose predicted foreground is empty is skipped (:414,421)
+        loss = 0
+        for b in range(B):
+            wb = 1.0 if sample_weight is None else float(sample_weight[b])
+            if wb != 0.0:
+                loss = loss + wb * F.cross_entropy(logits[[b]], labels[[b]], ignore_index=ign)
+        loss = loss / B
+    else:
+        loss = F.cross_entropy(logits, labels, ignore_index=ign)
+    if with_dice:
+        loss = loss + dice_loss_softmax(logits, labels)
+    return loss
+
+
+def dice_ce(logits, labels, with_dice=1, ignore_index=-1, per_sample=0, sample_weight=None, dtype=F64):
+    """logits [B, K, H, W], labels int64 [B, H, W] -> scalar"""
+    return _dice_ce(_c(logits, dtype), torch.as_tensor(labels).cpu(), with_dice, ignore_index, per_sample,
+                    None if sample_weight is None else _c(sample_weight, dtype)).detach()
+
+
+def dice_ce_bwd(logits, labels, gscale=1.0, with_dice=1, ignore_index=-1, per_sample=0, sample_weight=None, dtype=F64):
+    """-> gscale * d loss / d logits"""
+    logits = _c(logits, dtype).requires_grad_(True)
+    loss = _dice_ce(logits, torch.as_tensor(labels).cpu(), with_dice, ignore_index, per_sample,
+                    None if sample_weight is None else _c(sample_weight, dtype))
+    (g,) = torch.autograd.grad(loss, logits, torch.tensor(gscale, dtype=dtype))
+    return g
+
+
+# ------------------------------------------------------------------- alignLoss pieces (net/rp_net.py:412-417,433-436)
+def argmax_masks(pred, dtype=F64):
+    """pred [B, K, hw] -> (masks [B, K, hw] of 0 / 1, counts [B, K], keep [K, B])"""
+    pred = _c(pred, dtype)
+    am = pred.argmax(dim=1, keepdim=True)
+    masks = torch.cat([am == i for i in range(pred.shape[1])], dim=1).to(dtype)
+    counts = masks.sum(-1)
+    return masks, counts, (counts > 0).to(dtype).t().contiguous()
+
+
+def align_labels(fore, back):
+    lab = torch.full_like(torch.as_tensor(fore).cpu(), 255).long()
+    lab[torch.as_tensor(fore).cpu() == 1] = 1
+    lab[torch.as_tensor(back).cpu() == 1] = 0
+    return lab
+
+
+# --------------------------------------------------------------- pooling (net/unet.py:397, net/modules.py:66, net/vgg.py)
+def maxpool2(z, dtype=F64):
+    """z [N, H, W, C] -> [N, H/2, W/2, C]"""
+    return _nhwc(F.max_pool2d(_c(z, dtype).permute(0, 3, 1, 2), 2, 2))
+
+
+def maxpool2_bwd(z, dpool, skip=None, dtype=F64):
+    x = _c(z, dtype).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    (g,) = torch.autograd.grad(F.max_pool2d(x, 2, 2), x, _c(dpool, dtype).permute(0, 3, 1, 2))
+    g = _nhwc(g)
+    return g if skip is None else g + _c(skip, dtype)
+
+
+def upsample2_bwd(dyu, dtype=F64):
+    """dyu [N, H, W, C] -> dx [N, H/2, W/2, C]: autograd of nn.Upsample(scale_factor=2) (nearest)"""
+    dyu = _c(dyu, dtype).permute(0, 3, 1, 2)
+    N, C, H, W = dyu.shape
+    x = torch.zeros(N, C, H // 2, W // 2, dtype=dtype, requires_grad=True)
+    (g,) = torch.autograd.grad(F.interpolate(x, scale_factor=2), x, dyu)
+    return _nhwc(g)
+
+
+def maxpool3(z, stride, dtype=F64):
+    return _nhwc(F.max_pool2d(_c(z, dtype).permute(0, 3, 1, 2), 3, stride, 1))
+
+
+def maxpool3_bwd(z, dpool, stride, dtype=F64):
+    x = _c(z, dtype).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    (g,) = torch.autograd.grad(F.max_pool2d(x, 3, stride, 1), x, _c(dpool, dtype).permute(0, 3, 1, 2))
+    return _nhwc(g)
+
+
+def bias_relu_bwd(dz, z=None, dtype=F64):
+    """conv + bias (+ ReLU) backward given the OUTPUT z [P, C] (z = relu(a) and [z > 0] = [a > 0]): -> (dy [P, C], db [C])"""
+    dz = _c(dz, dtype)
+    a = (torch.zeros_like(dz) if z is None else _c(z, dtype)).requires_grad_(True)
+    b = torch.zeros(dz.shape[1], dtype=dtype, requires_grad=True)
+    out = a + b[None]
+    if z is not None:
+        out = torch.relu(out)
+    return torch.autograd.grad(out, (a, b), dz)
+
+
+# --------------------------------------------------------- soft-mask gradient (x * mask, x * (1 - mask); net/rp_net.py:283)
+def rowdot_scale(g, x, s, mode, dtype=F64):
+    """g, x [P, C], s [P] -> (dx [P, C], ds [P]) of y = x * s (mode 1) or x * (1 - s) (mode 2)"""
+    x, s = _c(x, dtype).requires_grad_(True), _c(s, dtype).requires_grad_(True)
+    y = x * (s if mode == 1 else 1 - s)[:, None]
+    return torch.autograd.grad(y, (x, s), _c(g, dtype))
+
+
+# ------------------------------------------------ fp16 tensor scale of a train-mode BatchNorm + ReLU output (include/rpnet_abi.h)
+def bn_act_bound(gamma, beta, n, dtype=F64):
+    """max_c |gamma_c| sqrt(n) + |beta_c|: |xhat| <= sqrt(n) for any batch of n values per channel"""
+    return (_c(gamma, dtype).abs() * float(n) ** 0.5 + _c(beta, dtype).abs()).max()

@@ -1,0 +1,68 @@
+"""CPU self-check of tests/ref64.py: its float64 functions agree with the oracle's restatement of the same operator sequences
+(oracle/rpnet_oracle.py, itself pinned to the reference's recorded values by test_oracle_golden.py) to 1e-12.  The two are
+written independently; ref64 is not built from the oracle."""
+import pytest
+import torch
+
+from tests import ref64 as R
+from tests.helpers import rel_err, rnd
+
+
+def nchw(f, h, w):
+    return f.reshape(f.shape[0], h, w, f.shape[-1]).permute(0, 3, 1, 2).contiguous()
+
+
+@pytest.mark.parametrize("B,C,H,W,h,w,nmask", [(2, 8, 24, 20, 6, 5, 3), (1, 64, 32, 32, 8, 8, 2)])
+def test_masked_pool_is_get_features_as_written(B, C, H, W, h, w, nmask):
+    from oracle import rpnet_oracle as O
+    f = rnd(1, B, h * w, C)
+    masks = (torch.rand(nmask, B, H, W, generator=torch.Generator().manual_seed(2)) > 0.5).float()
+    masks[-1] = 0                                   # an empty mask
+    fts = nchw(f, h, w).double()
+    ref = torch.stack([torch.cat([O.get_features_as_written(fts[[b]], masks[k, [b]].double()) for k in range(nmask)], 0)
+                       for b in range(B)], 0)
+    assert rel_err(R.masked_pool(f, masks, h, w), ref) < 1e-12
+    # the adjoint weights: the oracle's explicit tap construction against autograd of the up-sampler
+    am, msum = R.mask_adjoint(masks, h, w)
+    ref_am = O.bilinear_adjoint(masks.double(), h, w).reshape(nmask, B, h * w).transpose(0, 1)
+    assert rel_err(am, ref_am) < 1e-6               # the oracle builds its tap weights in float32
+    assert torch.equal(msum, masks.double().sum((2, 3)).t())
+
+
+@pytest.mark.parametrize("B,K,C,h,w", [(2, 2, 64, 8, 6), (1, 4, 8, 5, 7)])
+def test_cosine_match_is_cal_dist(B, K, C, h, w):
+    from oracle import rpnet_oracle as O
+    f, p = rnd(3, B, h * w, C), rnd(4, B, K, C)
+    fts = nchw(f, h, w).double()
+    ref = torch.stack([torch.stack([O.cal_dist(fts[[b]], p[b, [k]].double()) for k in range(K)], 1)[0] for b in range(B)], 0)
+    assert rel_err(R.cosine_match(f, p, 20.0).reshape(B, K, h, w), ref) < 1e-12
+
+
+@pytest.mark.parametrize("B,K,H,W", [(3, 2, 24, 20), (2, 4, 7, 5)])
+def test_dice_ce_is_the_oracles(B, K, H, W):
+    from oracle import rpnet_oracle as O
+    logits = rnd(5, B, K, H, W) * 2
+    labels = torch.randint(0, K, (B, H, W), generator=torch.Generator().manual_seed(6))
+    assert rel_err(R.dice_ce(logits, labels), O.dice_ce(logits.double(), labels)) < 1e-12
+    lg = logits.double().requires_grad_(True)
+    (g,) = torch.autograd.grad(O.dice_ce(lg, labels), lg)
+    assert rel_err(R.dice_ce_bwd(logits, labels), g) < 1e-12
+
+
+def test_per_sample_form_is_the_align_loss_term():
+    """per_sample = 1 with ignore_index = 255 and a zero weight is alignLoss's sum of per-episode F.cross_entropy calls over the
+    episodes that are not skipped, divided by the number of episodes (net/rp_net.py:343,349,414,421,438)"""
+    import torch.nn.functional as F
+    B, K, H, W = 3, 2, 12, 10
+    logits = rnd(7, B, K, H, W).double()
+    labels = torch.randint(0, K, (B, H, W), generator=torch.Generator().manual_seed(8))
+    labels[:, ::3] = 255
+    w = torch.tensor([1.0, 0.0, 1.0])
+    want = (F.cross_entropy(logits[[0]], labels[[0]], ignore_index=255) + F.cross_entropy(logits[[2]], labels[[2]], ignore_index=255)) / B
+    assert rel_err(R.dice_ce(logits, labels, with_dice=0, ignore_index=255, per_sample=1, sample_weight=w), want) < 1e-12
+
+
+def test_float32_is_the_same_code():
+    f, p = rnd(9, 2, 30, 16), rnd(10, 2, 3, 16)
+    a, b = R.cosine_match(f, p), R.cosine_match(f, p, dtype=torch.float32)
+    assert a.dtype == torch.float64 and b.dtype == torch.float32 and 0 < rel_err(b, a) < 1e-5
