@@ -11,6 +11,7 @@ is what the next convolution's operand loads read.  Those forms travel between l
 tensor, its planes, its tensor scale) — never as attributes on tensors, which any view or reshape would drop silently.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -47,9 +48,8 @@ _ASYNC = {"on": False, "side": {}, "pending": set(), "queued": False, "fifo": []
 # "f16" = ONE fp16 plane of operand / scale (plain fp16 operands, fp32 accumulation, fp32 BatchNorm statistics): the
 # reduced-precision arithmetic of BASELINE configs[4]; NOT fp32-equivalent (tolerances: DESIGN.md §6).
 _MODES = {"f32": (0, False, 0), "bf16x3": (3, False, 0), "f16x2": (3, True, 2), "f16": (3, True, 1)}
-_CORR16 = True
 # eval mode on predicted scales: the correlation kernel writes its own fp16 planes (False: a split pass behind it; A/B switch of round 6)
-_CORR_PRED_PLANES = True   # f16x2: the correlation on fp16 planes too (0: three bf16 planes)
+_CORR_PRED_PLANES = True
 _MATH = {}
 
 
@@ -64,9 +64,6 @@ set_conv_math(os.environ.get("RPNET_CONV_MATH", "f16x2"))
 
 def conv_math():
     return _MATH["mode"]
-
-
-import contextlib  # noqa: E402
 
 
 @contextlib.contextmanager
@@ -120,21 +117,6 @@ def set_async_wgrad(on=True):
     _ASYNC["on"] = bool(on)
 
 
-# diagnostic hook (None: off): a list that ConvBnRelu.backward fills with (tag, weight shape, clone) of its intermediate tensors
-# in stream order (round 4's diagnostic of the pooled-pass fault compared them between runs of one step)
-_TAPS = None
-
-
-_TAPS_PIN = False      # True: keep the tensors themselves (no copy kernel: the step's timing stays what it is, their memory is not reused)
-
-
-def _tap(tag, weight, *tensors):
-    if _TAPS is not None:
-        for i, t in enumerate(tensors):
-            if t is not None:
-                _TAPS.append((f"{tag}{i}", tuple(weight.shape), t.detach() if _TAPS_PIN else t.detach().clone()))
-
-
 def _direct(p, on=None):
     """on: the weight-gradient option the autograd node captured at forward time (None: the process-wide switch)"""
     if not ((_ASYNC["on"] if on is None else on) and p is not None and p.grad is not None and p.grad.is_contiguous()):
@@ -160,18 +142,16 @@ def _accumulate_direct(p, g, on=None):
     return None
 
 
-def use_compute_stream(device):
-    """The stream the step's main chain runs on: the caller's current stream.  (Round 3 tried a high-priority main stream:
-    +1 % alone, nothing on top of releasing every weight gradient behind its layer's dgrad — _WGRAD_DEFER — and removed.)"""
-    return torch.cuda.current_stream(device)
-
-
-def _reduce_stream(device):
-    key = ("reduce", device)
+def _stream(key, device):
     s = _ASYNC["side"].get(key)
     if s is None:
         s = _ASYNC["side"][key] = torch.cuda.Stream(device=device)
     return s
+
+
+def _reduce_stream(device):
+    """the stream of the reduce phase of a two-phase async weight gradient"""
+    return _stream(("reduce", device), device)
 
 
 # Two chains of one forward / backward pass on two streams that share BatchNorm modules (the support and the query call of
@@ -206,27 +186,17 @@ def _order_done(key):
 
 def _cre_stream(device):
     """the stream of the CRE's second branch (modules.ContextCorrelationEncoder.forward_masked, train mode)"""
-    key = ("cre", device)
-    s = _ASYNC["side"].get(key)
-    if s is None:
-        s = _ASYNC["side"][key] = torch.cuda.Stream(device=device)
-    return s
+    return _stream(("cre", device), device)
 
 
 def _pack_stream(device):
     """the stream of the per-step weight packing (WeightCache.prepack_async)"""
-    key = ("pack", device)
-    s = _ASYNC["side"].get(key)
-    if s is None:
-        s = _ASYNC["side"][key] = torch.cuda.Stream(device=device)
-    return s
+    return _stream(("pack", device), device)
 
 
 def _side_stream(device):
-    s = _ASYNC["side"].get(device)
-    if s is None:
-        s = _ASYNC["side"][device] = torch.cuda.Stream(device=device)
-    return s
+    """the stream of the async weight gradients"""
+    return _stream(device, device)
 
 
 def _defer_wgrad(launch):
@@ -543,8 +513,10 @@ class Operand:
         return Operand(x, scale=self.scale)
 
 
-# async weight gradients go out behind a dgrad (ConvBnRelu.backward): 1 = their own layer's, d = the one d - 1 layers further
-# down the chain (a deeper backlog of MFMA-bound work beside the chain's HBM-bound passes); 0 = in front of their own
+# async weight gradients go out behind a dgrad (ConvBnRelu.backward): 1 = their own layer's — the launch waits for it and starts when
+# the main chain enters the BatchNorm-backward passes of the layer below, so every HBM-bound pass of the chain has an MFMA-bound
+# partner; d = the one d - 1 layers further down the chain (a deeper backlog); 0 = in front of their own (the two GEMMs then share
+# the CUs, end together, and the passes behind them run alone)
 _WGRAD_DEFER = 1
 # A/B switch: split K for the eval-mode 3x3 convolutions whose grid covers half of the CUs or fewer
 _EVAL_SPLITK = True
@@ -613,19 +585,15 @@ def _split_operand(op, planes, scale=None, mode=0):
     return op.pbf
 
 
-# the 1x1 convolution over cat([corr, fm1]) on split planes too (gathering weight pack, per-source fp16 scales, single-tap
-# split weight gradient); _CONV1X1_SPLIT = False keeps it on the fp32-MFMA kernels (A/B switch)
-_CONV1X1_SPLIT = True
-
-
 def _use_split(pw, x0, x1):
     """convolutions whose channel counts fit the split pack run on the 16-bit matrix pipe when enabled: the 3x3 layers
-    (channel ranges in multiples of 32) and the 1x1 layer over two sources (its 121 + 256 channels are packed as 128 + 256)"""
+    (channel ranges in multiples of 32) and the 1x1 layer over cat([corr, fm1]) (its 121 + 256 channels are packed as 128 + 256:
+    gathering weight pack, per-source fp16 scales, single-tap split weight gradient)"""
     if not (_MATH["planes"] and pw is not None and x0.shape[-1] % 32 == 0 and (x1 is None or x1.shape[-1] % 32 == 0)):
         return False
     if pw.taps == 9:      # channel ranges in multiples of 32, or padded ranges through the gathering pack (mask_feature_map)
         return (pw.cin_pad == pw.cin and pw.cin % 32 == 0) or (pw.cin_pad != pw.cin and pw.cin_pad % 64 == 0)
-    return _CONV1X1_SPLIT and pw.taps == 1 and pw.cin_pad % 64 == 0 and pw.cout % 64 == 0 and x0.shape[-1] % 64 == 0
+    return pw.taps == 1 and pw.cin_pad % 64 == 0 and pw.cout % 64 == 0 and x0.shape[-1] % 64 == 0
 
 
 def split_f16(x, s_a, s_b=None, mask=None, mode=0, want_scale=True, planes=None, a_is_bound=False):
@@ -854,7 +822,6 @@ class WeightCache:
                 it.cin_off0, it.cin_split, it.cin_off1, it.cin_pad = pw.off0, pw.split, pw.off1, pw.cin_pad
             call("rpnet_pack_conv_weights_split", items, len(chunk), planes)
 
-
     def materialize(self, weights, planes):
         """Make every pack the layers of `weights` will read EXIST NOW, on the current stream (split packs of `planes`
         planes, or the fp32 packs when planes == 0; layers prepack() already served cost nothing).  RP_Net.forward calls
@@ -897,494 +864,533 @@ def _desc(x0, x1, w, bias, in_scale, in_mode, y0, y1, N, H, W, taps, ups, groups
 
 
 # ------------------------------------------------------------- conv + BN + ReLU
-class ConvBnRelu(Function):
-    """Conv2d(3x3 p1 | 1x1, bias) -> BatchNorm2d -> ReLU on NHWC activations
-    (net/modules.py:47-49,66-69; net/rp_net.py:50-59,65-69).
+# The arithmetic of one convolution launch (_conv_plan).  kind: "up4" (the collapsed up_conv on fp16 planes, see _UP4), "f16" (fp16
+# planes with tensor scales), "bf16" (three exact bf16 planes), "f32" (fp32 MFMA); planes: rpnet_conv_desc.split_planes; xs: the two
+# sources as the kernel reads them; w / col: the weight pack and its column scales; sx / sx1: tensor scales of fp16 sources (sx1
+# None: one joint scale).  A descriptor keeps its plan, and with it the planes and packs, alive.
+_Plan = collections.namedtuple("_Plan", "kind planes xs w sx sx1 col", defaults=(None, None, None))
 
-    x0 (,x1): sources concatenated along C; `in_scale` [N,h,w] with mode 1 (x*s) / 2 (x*(1-s));
-    `upsample`: nearest x2 in front of the conv; `groups`: BatchNorm statistic groups.
-    """
+
+def _conv_plan(pw, op0, op1, in_scale, in_mode, upsample, N, H, W, cout, up4_allowed=True):
+    """THE choice of a convolution's arithmetic (N, H, W: the output's): fp32 where the channel counts do not fit the split packs; fp16
+    planes where every source carries a bound (up_conv collapsed where it fits and is allowed); else three bf16 planes.  Makes missing planes / packs."""
+    x0, x1 = op0.x, None if op1 is None else op1.x
+    if not _use_split(pw, x0, x1):
+        return _Plan("f32", 0, (x0, x1), pw.wp)
+    f16 = _f16_sources(op0, op1, in_scale, in_mode, pw.taps == 1) if f16_mode() else None
+    if f16 is None:
+        np_ = _MATH["planes"]
+        xs = (_split_operand(op0, np_, in_scale, in_mode), None if op1 is None else _split_operand(op1, np_))
+        return _Plan("bf16", np_, xs, pw.split_packs(np_)[0])
+    fp = _MATH["f16_planes"]
+    up4 = up4_allowed and _up4_ok(pw, fp, upsample, x1, in_scale, f16[0], N, H, W, cout)
+    pk = pw.up4_packs(fp) if up4 else pw.split_packs(fp)
+    return _Plan("up4" if up4 else "f16", fp, (f16[0], f16[1]), pk[0], f16[2], f16[3], pk[2])
+
+
+def _conv_desc(plan, pw, bias, in_scale, in_mode, y, N, H, W, upsample, groups=1, ep_scale=None, ep_shift=None, ep_relu=0):
+    """the forward descriptor of a planned convolution: planes hold the x * mask factor (fp16: + scales, input-side zero-tile skip); fp32 kernels apply it"""
+    d = _desc(plan.xs[0], plan.xs[1], plan.w, bias, None if plan.planes else in_scale, in_mode, y, None, N, H, W, pw.taps, upsample,
+              groups, ep_scale, ep_shift, ep_relu)
+    d.split_planes, d._keep = plan.planes, plan
+    if 0 < plan.planes <= 2:
+        d.acc_scale_col, d.acc_scale_x, d.acc_scale_x1 = ptr(plan.col), ptr(plan.sx), ptr(plan.sx1)
+        if pw.taps == 9 and plan.xs[1] is None and not upsample:
+            _set_skip(d, in_scale, in_mode, 1, N, H, W)
+    return d
+
+
+def _dgrad_desc(pw, dys, sdy, dy, g0, g1, N, H, W, out_scale=None, out_mode=0, up4=False, skippable=False, skip_on=None):
+    """the input-gradient descriptor: the same implicit GEMM on dy with the flipped / transposed weight pack — on the planes dys (sdy: their
+    fp16 scale; up4: the collapsed pack) or, dys None, on fp32 dy.  out_scale / out_mode: the x * mask factor (skippable: + zero-tile skip)."""
+    if dys is None:
+        return _desc(dy, None, pw.wd, None, None, 0, g0, g1, N, H, W, pw.taps, 0, out_scale=out_scale, out_mode=out_mode)
+    np_ = dys.shape[0]
+    pk = pw.up4_packs(np_) if up4 else pw.split_packs(np_)
+    dd = _desc(dys, None, pk[1], None, None, 0, g0, g1, N, H, W, pw.taps, 1 if up4 else 0, out_scale=out_scale, out_mode=out_mode)
+    dd.split_planes = np_
+    if np_ <= 2:
+        dd.acc_scale_col, dd.acc_scale_x = ptr(pk[3]), ptr(sdy)
+        if skippable:
+            _set_skip(dd, out_scale, out_mode, 0, N, H, W, skip_on)
+    return dd
+
+
+_Req = collections.namedtuple("_Req", "z_unused pool pool_req defer_act eval_grad")      # what conv_bn_relu_op asks of the op ...
+
+
+class _Produced:
+    """... and what the op made beside its output tensor: fields of the output Operand, and whether a requested pool was fused"""
+    __slots__ = ("p16", "pbf", "scale", "planes_only", "deferred", "pooled")
+
+    def __init__(self):
+        self.p16 = self.pbf = self.scale = self.deferred = None
+        self.planes_only = self.pooled = False
+
+
+# what a backward reads (async_on / skip_on: the model's options when the node was made, rpnet_amd.schedule)
+_State = collections.namedtuple("_State", "shape groups bias beta bn_eval pool pw upsample in_mode xs sx sx1 up4 async_on skip_on")
+
+
+def _save_state(ctx, saved=None, shape=None, groups=1, bias=None, beta=None, bn_eval=False, pool=False, pw=None, upsample=0, in_mode=0, plan=None):
+    """saved: (x0, x1, in_scale, weight, gamma, y, stats), or None for the folded eval forward, which has no backward"""
+    if saved is None:
+        ctx.st = None
+        return
+    ctx.save_for_backward(*saved)
+    split = plan is not None and plan.planes
+    ctx.st = _State(shape, groups, bias, beta, bn_eval, pool, pw, upsample, in_mode, plan.xs if split else None,
+                    plan.sx if split else None, plan.sx1 if split else None, plan is not None and plan.kind == "up4", _ASYNC["on"], _MASK_SKIP)
+
+
+_NO_BACKWARD = ("rpnet_amd: an eval-mode layer made without a gradient-capable forward reached backward "
+                "(conv_bn_relu_op decides from torch.is_grad_enabled() and requires_grad at call time)")
+
+
+# ---- BatchNorm stages, shared by ConvBnRelu and Conv1BnRelu.  bnbuf = (running_mean, running_var, num_batches_tracked)
+def _want16(cout, out_split):      # does the output get an fp16 tensor scale (and, for a direct 3x3 / correlation consumer, planes)
+    return f16_mode() and cout % 32 == 0 and bool(out_split)
+
+
+def _eval_affine(pw, gamma, beta, bnbuf, cout):
+    """the folded eval-mode BatchNorm (scale, shift); it lives as long as the layer's packed weights"""
+    aff = getattr(pw, "eval_affine", None)
+    if aff is None:
+        aff = (_empty((cout,), gamma), _empty((cout,), gamma))
+        call("rpnet_bn_eval_affine", ptr(gamma), ptr(beta), ptr(bnbuf[0]), ptr(bnbuf[1]), BN_EPS, ptr(aff[0]), ptr(aff[1]), cout)
+        if pw is not None:
+            pw.eval_affine = aff
+    return aff
+
+
+def _eval_out16(res, z, mx, sp, z16, out_split):
+    """eval mode, want16: the output's fp16 scale / planes from the measured maximum mx, or on the predicted scale sp (z16: planes the epilogue wrote on it)"""
+    planes_out = out_split in (True, "corr")
+    if sp is not None:
+        res.scale = sp
+        if z16 is not None:
+            res.p16 = z16
+        elif planes_out:        # (first layer / fp32 kernels: a split pass, but no wait for the measured maximum)
+            res.p16 = split_f16(z, sp, want_scale=False)[0]
+    elif planes_out:            # planes and scale from the measured bound in one launch
+        res.p16, res.scale = split_f16(z, mx, a_is_bound=True)
+    else:
+        res.scale = torch.empty(1, device=z.device, dtype=torch.float32)
+        call("rpnet_pow2_scale", ptr(mx), ptr(res.scale))
+
+
+def _bn_batch_stats(y, part, fused, shape, groups, gamma, beta, bnbuf):
+    """train mode -> stats [4][groups][cout] = (scale, shift, mean, invstd) of the batch (from the `fused` partial rows the conv
+    launch summed, or from a pass over y), and the running-statistics update"""
+    N, H, W, cout = shape
+    stats = _empty((4, groups, cout), gamma)
+    rm, rv, nbt = bnbuf
+    _order_wait(gamma.data_ptr())      # the running statistics: after the other chain's update of this module
+    if fused:
+        call("rpnet_bn_stats_from_partial", ptr(part), fused, N, H * W, cout, groups, ptr(gamma), ptr(beta), ptr(rm), ptr(rv),
+             ptr(nbt), BN_MOMENTUM, BN_EPS, ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]))
+    else:
+        wsb = query("rpnet_bn_workspace_bytes", cout, groups)
+        ws = _ws(wsb, gamma)
+        call("rpnet_bn_stats", ptr(y), N, H * W, cout, groups, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), ptr(nbt), BN_MOMENTUM,
+             BN_EPS, ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(ws), wsb)
+    _order_done(gamma.data_ptr())
+    return stats
+
+
+def _bn_output(y, stats, shape, groups, gamma, beta, out_split, req, res, pool_ok, conv1=None):
+    """train mode: BatchNorm + ReLU -> z, also as the planes / with the fp16 scale its consumer reads (out_split: see conv_bn_relu_op).  pool_ok: the
+    layer runs on split planes forward AND backward (its dy exists as planes).  conv1: (image, weight, bias) of a first layer without y (_CONV1_RECOMP)."""
+    N, H, W, cout = shape
+    planes_out = out_split in (True, "corr")
+    want16 = _want16(cout, out_split)
+    np_out = 0
+    if planes_out and cout % 32 == 0 and _MATH["planes"]:
+        np_out = _MATH["f16_planes"] if want16 else _MATH["planes"]
+    # pool: BatchNorm + ReLU + MaxPool2d(2, 2) in one pass (the output feeds nothing but its pool)
+    pool = res.pooled = bool(pool_ok and np_out > 0 and out_split is True and H % 2 == 0 and W % 2 == 0)
+    Hz, Wz = (H // 2, W // 2) if pool else (H, W)
+    dev = gamma.device
+    zs = torch.empty((np_out, N, Hz, Wz, cout), device=dev, dtype=torch.float16 if np_out <= 2 else torch.bfloat16) if np_out else None
+    sz = torch.empty(1, device=dev, dtype=torch.float32) if want16 else None
+    if req.z_unused and want16 and np_out and (pool or not req.pool_req):
+        # the single consumer reads the fp16 planes: no fp32 form, z is a zero-storage placeholder for autograd (an unfused pool keeps fp32)
+        z = torch.empty(1, device=dev, dtype=torch.float32).expand(N, Hz, Wz, cout)
+        res.planes_only = True
+    else:
+        z = torch.empty((N, Hz, Wz, cout), device=dev, dtype=torch.float32)
+    if req.defer_act and not (pool or np_out or want16 or res.planes_only) and conv1 is None and groups == 1:
+        # BatchNorm + ReLU are applied by the consumer's fused launch (CosineMatchUp, rpnet_refine_glue_fwd), which fills z
+        res.deferred = (y, stats[0], stats[1])
+    elif conv1 is not None:
+        if not (res.planes_only and np_out):
+            raise RuntimeError("rpnet_amd: the first layer was run without its pre-BatchNorm tensor but its output is not planes-only")
+        call("rpnet_conv1_bn_relu", ptr(conv1[0]), ptr(conv1[1]), ptr(conv1[2]), ptr(stats[0]), ptr(stats[1]), None, ptr(zs), np_out,
+             ptr(gamma), ptr(beta), ptr(sz), N, H, W, cout, groups)
+        ARITH[("bn_relu", "first layer made again from the image")] += 1
+    else:
+        # the tensor scale comes out of the same launch: with the fp16 planes, or alone (np_out == 0, "scale")
+        call("rpnet_bn_relu", ptr(y), ptr(stats[0]), ptr(stats[1]), None if res.planes_only else ptr(z), ptr(zs), np_out, ptr(gamma),
+             ptr(beta), ptr(sz), N, H * W, cout, groups, W if pool else 0, None, 0)
+    if pool:
+        ARITH[("bn_relu", "with the 2x2 max-pool")] += 1
+    if want16 and np_out:
+        res.p16 = zs          # the next convolution's operand, produced here instead of by a separate pass
+    else:
+        res.pbf = zs
+    res.scale = sz
+    return z
+
+
+def _bn_eval_grad_output(y, gamma, beta, bnbuf, out_split, res):
+    """eval mode with a gradient -> (z = relu(y scale + shift), stats [4][1][cout] = (scale, shift, running mean, running invstd)); planes / scale from max |z|"""
+    N, H, W, cout = y.shape
+    stats = _empty((4, 1, cout), y)
+    call("rpnet_bn_eval_affine", ptr(gamma), ptr(beta), ptr(bnbuf[0]), ptr(bnbuf[1]), BN_EPS, ptr(stats[0]), ptr(stats[1]), cout)
+    stats[2, 0].copy_(bnbuf[0])
+    torch.rsqrt(bnbuf[1] + BN_EPS, out=stats[3, 0])
+    z = torch.empty_like(y)
+    mx = torch.zeros(1, device=y.device, dtype=torch.float32)
+    call("rpnet_bn_eval_relu", ptr(y), ptr(stats[0]), ptr(stats[1]), ptr(z), ptr(mx), N * H * W, cout)
+    ARITH[("bn_relu", "eval mode, with a gradient")] += 1
+    if _want16(cout, out_split):
+        _eval_out16(res, z, mx, None, None, out_split)
+    return z, stats
+
+
+def _bn_backward(dz, y, stats, gamma, beta, shape, groups, async_on, bn_eval=False, np_=0, want_dy=True, pool_w=0, part=None, rows=0):
+    """BatchNorm backward: reduction, dgamma / dbeta (into the gradient bucket where allowed), apply pass -> (dy, dys, sdy, dgamma, dbeta, ws).  dy: fp32
+    (want_dy) and / or np_ planes dys (sdy: fp16 scale); neither: only the coefficients in ws.  pool_w: dz is POOLED.  part / rows: a first layer without y."""
+    N, H, W, cout = shape
+    wsb = query("rpnet_bn_workspace_bytes", cout, groups)
+    ws = _ws(wsb, dz)
+    dys = torch.empty((np_, N, H, W, cout), device=dz.device, dtype=torch.bfloat16) if np_ else None
+    sdy = torch.empty(1, device=dz.device, dtype=torch.float32) if 0 < np_ <= 2 else None      # fp16: tensor scale
+    dy = _empty(shape, dz) if want_dy else None
+    # straight into the gradient bucket, no AccumulateGrad add (eval mode: the conv bias gradient is made from dbeta)
+    direct = _direct(gamma, async_on) and _direct(beta, async_on) and not bn_eval
+    dgamma, dbeta = (None, None) if direct else (_empty((cout,), dz), _empty((cout,), dz))
+    ARITH[("bn_bwd", "first layer made again from the image" if part is not None else "eval mode" if bn_eval else "own reduction pass")] += 1
+    if direct:
+        _order_wait(gamma.data_ptr())  # gamma.grad / beta.grad: after the other chain's accumulation into them
+    if bn_eval:      # running statistics: dy = scale dz m, nothing subtracted; the coefficients in ws are zero
+        call("rpnet_bn_eval_bwd", ptr(dz), ptr(y), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(dy), ptr(dys), np_,
+             ptr(sdy), ptr(dgamma), ptr(dbeta), N, H * W, cout, groups, 0, ptr(ws), wsb)
+    else:
+        call("rpnet_bn_bwd", ptr(dz), ptr(y), ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(dy), ptr(dys),
+             np_, ptr(sdy), ptr(gamma.grad if direct else dgamma), ptr(beta.grad if direct else dbeta), N, H * W, cout, groups,
+             1 if direct else 0, ptr(part), None, rows, pool_w, ptr(ws), wsb, None, 0)
+    if direct:
+        _order_done(gamma.data_ptr())
+    return dy, dys, sdy, dgamma, dbeta, ws
+
+
+def _bias_grad(bias, gamma, stats, dbeta, bn_eval, async_on):
+    if bn_eval:      # eval mode: d(bias) = sum over pixels of dy = scale dbeta (the running statistics do not absorb it)
+        return _accumulate_direct(bias, stats[0, 0] * dbeta, async_on)
+    return None if _direct(bias, async_on) else torch.zeros_like(gamma)      # in front of a train-mode BatchNorm: analytically zero
+
+
+# ---- weight gradient: what it computes (_wgrad_entry) apart from when and where it runs (_schedule_wgrad)
+def _wgrad_entry(st, x0, x1, in_scale, dy, dys, sdy, wsplit):
+    """-> (descriptor: the forward's gather, dy the other operand; wgrad(dy_ptr, dw_ptr, ws): GEMM (dw_ptr None) / reduce (dy_ptr None) / both; ws bytes)"""
+    pw = st.pw
+    N, H, W, cout = st.shape
+    if wsplit:       # both operands as split planes (the x * mask factor is already in xs)
+        d = _desc(st.xs[0], st.xs[1], None, None, None, 0, None, None, N, H, W, pw.taps, st.upsample, co_split=(cout, 0), wgrad=True)
+        d.split_planes = np_ = dys.shape[0]
+        if np_ <= 2:
+            d.acc_scale_x, d.acc_scale_dy, d.acc_scale_x1 = ptr(st.sx), ptr(sdy), ptr(st.sx1)
+    else:
+        d = _desc(x0, x1, None, None, in_scale, st.in_mode, dy, None, N, H, W, pw.taps, st.upsample, wgrad=True)
+    # the collapsed up_conv (see _UP4): sixteen tap products per source pixel instead of thirty-six
+    up4 = bool(st.up4 and wsplit and np_ in (1, 2) and query("rpnet_conv_wgrad_up4_supported", C.byref(d)))
+    wb = (query("rpnet_conv_wgrad_up4_workspace_bytes", N, H, W, pw.cin, cout) if up4 else
+          query("rpnet_conv_wgrad_workspace_bytes", N, H, W, pw.cin_pad, cout, pw.taps))
+
+    def wgrad(dy_ptr, dw_ptr, ws):
+        if not up4:
+            _cconv("rpnet_conv_wgrad", d, dy_ptr, dw_ptr, pw.cin, pw.off0, pw.split, pw.off1, ptr(ws), wb)
+            return
+        ARITH[("wgrad3x3_up4", _PLANE_NAME[d.split_planes])] += dy_ptr is not None      # (the reduce-only phase is not a second launch)
+        call("rpnet_conv_wgrad_up4", C.byref(d), dy_ptr, dw_ptr, ptr(ws), wb)
+    return d, wgrad, wb
+
+
+def _schedule_wgrad(d, wgrad, wb, dyp, two_phase, weight, async_on, keep):
+    """Run a weight gradient: inline -> (dw, False); or, in bucket mode, accumulated into weight.grad on the side stream (two_phase: the
+    GEMM there, its HBM-bound reduce on a third stream) -> (None, deferred: queued, the caller releases it behind its dgrad).  keep: what it reads."""
+    dev = weight.device
+    if not _direct(weight, async_on):
+        dw = torch.empty_like(weight)
+        wgrad(ptr(dyp), ptr(dw), _ws(wb, weight))
+        return dw, False
+    # the stream this node runs on (it produced dy and runs this layer's dgrad), taken NOW: a deferred launch may be released by a
+    # later node on another stream (the CRE's second branch, the encoder's second chain), and must still wait for THIS one
+    prod = torch.cuda.current_stream(dev)
+
+    def launch_async():
+        side = _side_stream(dev)
+        side.wait_stream(prod)                   # dy, x are ready on the producing stream (deferred: and the dgrad is done)
+        d.accumulate = 1
+        with torch.cuda.stream(side):
+            ws = _ws(wb, weight)
+            if two_phase:
+                wgrad(ptr(dyp), None, ws)
+                red = _reduce_stream(dev)
+                red.wait_stream(side)
+                _ASYNC["keep"].append(ws)        # read by the reduce; alive until join_side_streams
+                with torch.cuda.stream(red):
+                    wgrad(None, ptr(weight.grad), ws)
+            else:
+                wgrad(ptr(dyp), ptr(weight.grad), ws)
+        _ASYNC["keep"].append(keep)              # alive until join_side_streams (the saved tensors outlive this node anyway)
+        if not _ASYNC["queued"]:      # once per backward pass (reset_async re-arms it after a failed one)
+            torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
+            _ASYNC["queued"] = True
+        _ASYNC["pending"].add(dev)
+    if _WGRAD_DEFER:
+        _defer_wgrad(launch_async)
+        return None, True
+    launch_async()
+    return None, False
+
+
+def _input_grad(st, dy, dys, sdy, x0, x1, mask, dsplit):
+    """launch the input gradient -> (g0, g1, collapsed: the up4 form, at the SOURCE resolution).  mask: the x * mask factor the launch applies"""
+    pw = st.pw
+    N, H, W, _ = st.shape
+    if st.up4 and dsplit and dys.shape[0] in (1, 2):
+        g0 = _empty(x0.shape, dys)
+        dd = _dgrad_desc(pw, dys, sdy, None, g0, None, N, H, W, up4=True)
+        if query("rpnet_conv_up4_supported", C.byref(dd), 2):
+            _cup4(dd, 2)
+            return g0, None, True
+    g0 = _empty((N, H, W, x0.shape[-1]), x0)
+    g1 = _empty((N, H, W, x1.shape[-1]), x0) if x1 is not None else None
+    dd = _dgrad_desc(pw, dys if dsplit else None, sdy, dy, g0, g1, N, H, W, mask, st.in_mode,
+                     skippable=pw.taps == 9 and x1 is None and not st.upsample, skip_on=st.skip_on)
+    _cconv("rpnet_conv_fwd", dd)
+    return g0, g1, False
+
+
+class ConvBnRelu(Function):
+    """Conv2d(3x3 p1 | 1x1, bias) -> BatchNorm2d -> ReLU on NHWC activations, the layers with packed weights (Cin >= 32)
+    (net/modules.py:47-49,66-69; net/rp_net.py:50-59,65-69).  x0 (,x1): sources concatenated along C; `in_scale` [N,h,w] with mode
+    1 (x*s) / 2 (x*(1-s)); `upsample`: nearest x2 in front of the conv; `groups`: BatchNorm statistic groups."""
 
     @staticmethod
-    def forward(ctx, x0, x1, in_scale, weight, bias, gamma, beta, running_mean, running_var, nbt, pw, training,
-                groups, upsample, in_mode, out_split, ops, produced):
-        """ops = (Operand of x0, Operand of x1 or None): the planes / scales of the sources; `produced` (a dict) receives
-        the planes / scale this launch wrote for the output ("p16", "pbf", "scale") — conv_bn_relu_op builds the
-        output Operand from it."""
+    def forward(ctx, x0, x1, in_scale, weight, bias, gamma, beta, bnbuf, pw, cfg, ops, req, res):
+        """cfg = (training, groups, upsample, in_mode, out_split); ops = (Operand of x0, Operand of x1 or None): the planes / scales
+        of the sources; req (_Req): what the caller asked for; res (_Produced): receives what the launches made for the output"""
         hip.require_gpu(x0, weight)
+        training, groups, upsample, in_mode, out_split = cfg
         op0, op1 = ops
         N, Hs, Ws, _ = x0.shape
         H, W = (Hs * 2, Ws * 2) if upsample else (Hs, Ws)
         cout = weight.shape[0]
-        first = weight.shape[1] == 1 and weight.shape[2] == 3  # Cin = 1 direct convolution
-        z = _empty((N, H, W, cout), x0)
-        # eval mode with a gradient (produced["eval_grad"], set by conv_bn_relu_op): the convolution writes the pre-BatchNorm y
-        # for the backward, the running-statistics affine and ReLU follow in their own pass (rpnet_bn_eval_relu)
-        bn_eval = not training
-        if bn_eval and not produced.get("eval_grad"):
-            aff = getattr(pw, "eval_affine", None)     # the folded BatchNorm lives as long as the layer's packed weights
-            if aff is None:
-                aff = (_empty((cout,), x0), _empty((cout,), x0))
-                call("rpnet_bn_eval_affine", ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), BN_EPS, ptr(aff[0]),
-                     ptr(aff[1]), cout)
-                if pw is not None:
-                    pw.eval_affine = aff
-            scale, shift = aff
-            # f16x2 / f16 in eval mode: running statistics give no a-priori bound of the output, so the launch measures
-            # one — max |z| through rpnet_conv_desc.out_absmax — and the fp16 tensor scale (and, for a direct 3x3 /
-            # correlation consumer, the planes) follow from it; an output that wants neither keeps the plain path.
-            want16 = f16_mode() and cout % 32 == 0 and bool(out_split) and (_CORR16 or out_split != "corr")
-            mx = _absmax_slot(x0.device) if want16 else None
-            sp = pred_scale(x0.device) if want16 else None      # predicted scale of this launch (None: this call measures)
-            np_out = _MATH["planes"] if (out_split in (True, "corr") and cout % 32 == 0 and not first and not want16) else 0
-            zs = torch.empty((np_out, N, H, W, cout), device=x0.device, dtype=torch.bfloat16) if np_out else None
-            z16 = None
-            if first:
-                call("rpnet_conv1_fwd", ptr(x0), ptr(weight), ptr(bias), ptr(z), ptr(scale), ptr(shift), N, H, W, cout, ptr(mx),
-                     None, 1)
-            elif _use_split(pw, x0, x1):
-                f16 = _f16_sources(op0, op1, in_scale, in_mode, pw.taps == 1) if f16_mode() else None
-                up4e = False
-                if f16 is not None:      # fp16 planes of the sources (their scales measured by their own launches)
-                    fp = _MATH["f16_planes"]
-                    # up_conv in eval mode on its collapsed four-tap form too (round 6; training: round 5): the folded BatchNorm affine,
-                    # ReLU and the measured maximum are the up4 kernel's plain epilogue; its output feeds a concatenation, which
-                    # splits the fp32 tensor itself (out_split "scale": no planes wanted from this launch)
-                    up4e = out_split in ("scale", False) and _up4_ok(pw, fp, upsample, x1, in_scale, f16[0], N, H, W, cout)
-                if up4e:
-                    pk4 = pw.up4_packs(fp)
-                    d = _desc(f16[0], None, pk4[0], bias, None, 0, z, None, N, H, W, pw.taps, 1, 1, scale, shift, 1)
-                    d.split_planes = fp
-                    d.acc_scale_col, d.acc_scale_x = ptr(pk4[2]), ptr(f16[2])
-                    d._keep = (f16, pk4)
-                elif f16 is not None:
-                    wps, _, t_row, _ = pw.split_packs(fp)
-                    d = _desc(f16[0], f16[1], wps, bias, None, 0, z, None, N, H, W, pw.taps, upsample, 1, scale, shift, 1)
-                    d.split_planes = fp
-                    d.acc_scale_col, d.acc_scale_x, d.acc_scale_x1 = ptr(t_row), ptr(f16[2]), ptr(f16[3])
-                    d._keep = f16
-                    if pw.taps == 9 and x1 is None and not upsample:
-                        _set_skip(d, in_scale, in_mode, 1, N, H, W)
-                else:
-                    np_ = _MATH["planes"]
-                    d = _desc(_split_operand(op0, np_, in_scale, in_mode), None if x1 is None else _split_operand(op1, np_),
-                              pw.split_packs(np_)[0], bias, None, 0, z, None, N, H, W, pw.taps, upsample, 1, scale, shift, 1)
-                    d.split_planes = np_
-                if up4e:
-                    d.out_absmax = ptr(mx)
-                else:
-                    d.y_split, d.split_out_planes, d.out_absmax = ptr(zs), np_out, ptr(mx)
-                if sp is not None and out_split in (True, "corr") and not up4e:
-                    # the fp16 planes of output / predicted scale straight out of the epilogue: no second pass over z
-                    fpo = _MATH["f16_planes"]
-                    z16 = torch.empty((fpo, N, H, W, cout), device=x0.device, dtype=torch.float16)
-                    d.y_split, d.split_out_planes, d.y_split_scale = ptr(z16), fpo, ptr(sp)
-                if up4e:
-                    _cup4(d, 1)
-                else:
-                    if _EVAL_SPLITK and d.split_planes == 2 and pw.taps == 9 and N * H * W * cout <= 128 * 256 * 64:
-                        # a grid that would leave half of the CUs idle (batch-2 calls): lend the workspace that lets the launch
-                        # cut its K range into parts (rpnet_conv_desc.splitk_ws)
-                        nb = query("rpnet_conv_splitk_workspace_bytes", C.byref(d))
-                        if nb:
-                            d._ws = _ws(nb, x0)
-                            d.splitk_ws, d.splitk_ws_bytes = ptr(d._ws), nb
-                    _cconv("rpnet_conv_fwd", d)
-            else:
-                d = _desc(x0, x1, pw.wp, bias, in_scale, in_mode, z, None, N, H, W, pw.taps, upsample, 1, scale, shift, 1)
-                d.y_split, d.split_out_planes, d.out_absmax = ptr(zs), np_out, ptr(mx)
-                _cconv("rpnet_conv_fwd", d)
-            if zs is not None:
-                produced["pbf"] = zs      # written by the conv epilogue: no separate split pass in eval mode
-            if want16 and sp is not None:
-                if z16 is not None:
-                    produced["p16"], produced["scale"] = z16, sp
-                elif out_split in (True, "corr"):   # (first layer / fp32 kernels: a split pass, but no wait for the measured maximum)
-                    produced["p16"], produced["scale"] = split_f16(z, sp, want_scale=False)[0], sp
-                else:
-                    produced["scale"] = sp
-            elif want16:
-                if out_split in (True, "corr"):     # planes and scale from the measured bound in one launch
-                    produced["p16"], produced["scale"] = split_f16(z, mx, a_is_bound=True)
-                else:
-                    sz = torch.empty(1, device=x0.device, dtype=torch.float32)
-                    call("rpnet_pow2_scale", ptr(mx), ptr(sz))
-                    produced["scale"] = sz
-            ctx.eval_mode = True
-            return z
-        # the first layer on fp16 planes whose only consumer reads the planes: y is summed, never written (see _CONV1_RECOMP)
-        if bn_eval:
+        shape = (N, H, W, cout)
+        if not training and not req.eval_grad:
+            _save_state(ctx)
+            return _folded_eval_conv(x0, in_scale, bias, gamma, beta, bnbuf, pw, shape, upsample, in_mode, out_split, op0, op1, res)
+        # train / eval with a gradient: the conv writes the pre-BatchNorm y; up4 whatever the consumer reads (the planes come from the BN pass)
+        if not training:
             groups = 1       # running statistics: one affine for every image
-        recomp = bool(not bn_eval and first and _CONV1_RECOMP and f16_mode() and cout % 8 == 0 and 256 % (cout // 8) == 0 and out_split is True
-                      and produced.get("z_unused") and not produced.get("pool_req") and _CONV1_BN_FUSE
-                      and query("rpnet_conv1_stats_blocks", N, H, W, cout, groups) > 0)
-        y = None if recomp else _empty((N, H, W, cout), x0)
-        stats = _empty((4, groups, cout), x0)  # scale, shift, mean, invstd
-        fused, xs, sx, sx1 = 0, None, None, None
-        if first:      # batch statistics out of the same launch (one partial row per block and group)
-            fused = 0 if bn_eval else query("rpnet_conv1_stats_blocks", N, H, W, cout, groups)
-            part = torch.empty(groups * fused * cout * 2, device=x0.device, dtype=torch.float64) if fused else None
-            call("rpnet_conv1_fwd", ptr(x0), ptr(weight), ptr(bias), ptr(y), None, None, N, H, W, cout, None, ptr(part), groups)
+        plan = _conv_plan(pw, op0, op1, in_scale, in_mode, upsample, N, H, W, cout)
+        f16 = plan.planes in (1, 2)
+        ok0 = not op0.planes_only or (f16 and op1 is None and in_scale is None and pw.cin % 64 == 0 and cout % 64 == 0)
+        ok1 = op1 is None or not op1.planes_only or (f16 and plan.xs[1] is op1.p16 and pw.cin_pad % 64 == 0 and cout % 64 == 0
+                                                     and x0.shape[-1] % 64 == 0)
+        if not (ok0 and ok1):
+            raise RuntimeError("rpnet_amd: a planes-only operand (conv_bn_relu_op(z_unused=True)) reached a convolution that cannot "
+                               "run forward AND weight gradient from its fp16 planes as they are")
+        y = _empty(shape, x0)
+        d = _conv_desc(plan, pw, bias, in_scale, in_mode, y, N, H, W, upsample, groups)
+        up4 = plan.kind == "up4"
+        fused = query("rpnet_conv_up4_stats_blocks" if up4 else "rpnet_conv_stats_blocks", C.byref(d)) if training else 0
+        part = None
+        if fused:  # batch statistics come out of the conv epilogue: y is not re-read
+            part = torch.empty(groups * fused * cout * 2, device=x0.device, dtype=torch.float64)
+            d.stats_partial = ptr(part)
+        if up4:
+            _cup4(d, 1)
         else:
-            f16 = _f16_sources(op0, op1, in_scale, in_mode, pw.taps == 1) if (f16_mode() and _use_split(pw, x0, x1)) else None
-            if op0.planes_only and not (f16 is not None and op1 is None and in_scale is None and pw.cin % 64 == 0 and cout % 64 == 0):
-                raise RuntimeError("rpnet_amd: a planes-only operand (conv_bn_relu_op(z_unused=True)) reached a convolution "
-                                   "that cannot run forward AND weight gradient from its fp16 planes")
-            if op1 is not None and op1.planes_only and not (f16 is not None and f16[1] is op1.p16 and pw.cin_pad % 64 == 0
-                                                            and cout % 64 == 0 and x0.shape[-1] % 64 == 0):
-                raise RuntimeError("rpnet_amd: a planes-only second source reached a convolution that does not read its "
-                                   "fp16 planes as they are (forward and weight gradient)")
-            up4 = False
-            if f16 is not None:      # fp16 planes (two, or one in "f16" mode) with a tensor scale; weights with row scales
-                xs, sx, sx1 = (f16[0], f16[1]), f16[2], f16[3]
-                fp = _MATH["f16_planes"]
-                up4 = _up4_ok(pw, fp, upsample, x1, in_scale, xs[0], N, H, W, cout)
-                wps, t_row = (pw.up4_packs(fp)[0], pw.up4_packs(fp)[2]) if up4 else (pw.split_packs(fp)[0], pw.split_packs(fp)[2])
-                d = _desc(xs[0], xs[1], wps, bias, None, 0, y, None, N, H, W, pw.taps, upsample, groups)
-                d.split_planes = fp
-                d.acc_scale_col, d.acc_scale_x, d.acc_scale_x1 = ptr(t_row), ptr(sx), ptr(sx1)
-                if pw.taps == 9 and x1 is None and not upsample:
-                    _set_skip(d, in_scale, in_mode, 1, N, H, W)
-            elif _use_split(pw, x0, x1):
-                np_ = _MATH["planes"]
-                xs = (_split_operand(op0, np_, in_scale, in_mode), None if x1 is None else _split_operand(op1, np_))
-                d = _desc(xs[0], xs[1], pw.split_packs(np_)[0], bias, None, 0, y, None, N, H, W, pw.taps, upsample, groups)
-                d.split_planes = np_
-            else:
-                d = _desc(x0, x1, pw.wp, bias, in_scale, in_mode, y, None, N, H, W, pw.taps, upsample, groups)
-            fused = 0 if bn_eval else query("rpnet_conv_up4_stats_blocks" if up4 else "rpnet_conv_stats_blocks", C.byref(d))
-            if fused:  # batch statistics come out of the conv epilogue: y is not re-read
-                part = torch.empty(groups * fused * cout * 2, device=x0.device, dtype=torch.float64)
-                d.stats_partial = ptr(part)
-            if up4:
-                _cup4(d, 1)
-            else:
-                _cconv("rpnet_conv_fwd", d)
-        if bn_eval:
-            return ConvBnRelu._eval_grad_tail(ctx, x0, x1, in_scale, weight, bias, gamma, beta, running_mean, running_var, y,
-                                              z, pw, upsample, in_mode, first, out_split, produced, xs, sx, sx1,
-                                              (not first) and up4)
-        _order_wait(gamma.data_ptr())      # the running statistics: after the other chain's update of this module
-        if fused:
-            call("rpnet_bn_stats_from_partial", ptr(part), fused, N, H * W, cout, groups, ptr(gamma), ptr(beta),
-                 ptr(running_mean), ptr(running_var), ptr(nbt), BN_MOMENTUM, BN_EPS, ptr(stats[0]), ptr(stats[1]),
-                 ptr(stats[2]), ptr(stats[3]))
+            _cconv("rpnet_conv_fwd", d)
+        if training:
+            stats = _bn_batch_stats(y, part, fused, shape, groups, gamma, beta, bnbuf)
+            pool_ok = req.pool and plan.planes and pw.cin_pad % 64 == 0 and cout % 64 == 0 and x0.shape[-1] % 64 == 0
+            z = _bn_output(y, stats, shape, groups, gamma, beta, out_split, req, res, pool_ok)
         else:
-            wsb = query("rpnet_bn_workspace_bytes", cout, groups)
-            ws = _ws(wsb, x0)
-            call("rpnet_bn_stats", ptr(y), N, H * W, cout, groups, ptr(gamma), ptr(beta), ptr(running_mean),
-                 ptr(running_var), ptr(nbt), BN_MOMENTUM, BN_EPS, ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]),
-                 ptr(ws), wsb)
-        _order_done(gamma.data_ptr())
-        # the output also as the operand planes of its consumer: out_split True = a 3x3 convolution reads it as is (fp16
-        # planes with the tensor scale in f16x2 mode), "corr" = the local correlation (bf16 planes), "scale" = no planes
-        # but the fp16 tensor scale (pooled / concatenated / masked 3x3 consumers split the fp32 tensor), False = none
-        want16 = f16_mode() and cout % 32 == 0 and out_split in ((True, "scale", "corr") if _CORR16 else (True, "scale"))
-        np_out = 0
-        if out_split in (True, "corr") and cout % 32 == 0 and _MATH["planes"]:
-            np_out = _MATH["f16_planes"] if want16 else _MATH["planes"]
-        # pool: BatchNorm + ReLU + MaxPool2d(2, 2) in one pass (the output feeds nothing but its pool): possible when this
-        # layer runs on split planes forward AND backward (its dy then exists as planes: the pooled backward writes those)
-        pool = bool(produced.get("pool")) and np_out > 0 and out_split is True and xs is not None and not first and \
-            H % 2 == 0 and W % 2 == 0 and pw.cin_pad % 64 == 0 and cout % 64 == 0 and x0.shape[-1] % 64 == 0
-        produced["pooled"] = pool
-        Hz, Wz = (H // 2, W // 2) if pool else (H, W)
-        if pool:
-            z = _empty((N, Hz, Wz, cout), x0)
-        zs = torch.empty((np_out, N, Hz, Wz, cout), device=x0.device, dtype=torch.float16 if np_out <= 2 else torch.bfloat16) if np_out else None
-        sz = torch.empty(1, device=x0.device, dtype=torch.float32) if want16 else None
-        if produced.get("z_unused") and want16 and np_out and out_split in (True, "corr") and (pool or not produced.get("pool_req")):
-            # the single consumer reads the fp16 planes: the fp32 form is never written, z is a zero-storage placeholder
-            # of the right shape for autograd (a pool request that could not be fused keeps the fp32 form: the separate
-            # max-pool reads it)
-            z = torch.empty(1, device=x0.device, dtype=torch.float32).expand(N, Hz, Wz, cout)
-            produced["planes_only"] = True
-        defer = (bool(produced.get("defer_act")) and not pool and not np_out and not want16 and not recomp
-                 and groups == 1 and not produced.get("planes_only"))
-        if defer:
-            # BatchNorm + ReLU are applied by the consumer's fused launch (CosineMatchUp, rpnet_refine_glue_fwd), which fills z
-            produced["deferred"] = (y, stats[0], stats[1])
-        elif recomp:
-            if not (produced.get("planes_only") and want16 and np_out):
-                raise RuntimeError("rpnet_amd: the first layer was run without its pre-BatchNorm tensor but its output is not planes-only")
-            call("rpnet_conv1_bn_relu", ptr(x0), ptr(weight), ptr(bias), ptr(stats[0]), ptr(stats[1]), None, ptr(zs), np_out,
-                 ptr(gamma), ptr(beta), ptr(sz), N, H, W, cout, groups)
-            ARITH[("bn_relu", "first layer made again from the image")] += 1
-        else:
-            # the tensor scale comes out of the same launch: with the fp16 planes, or alone (np_out == 0, "scale")
-            call("rpnet_bn_relu", ptr(y), ptr(stats[0]), ptr(stats[1]), None if produced.get("planes_only") else ptr(z), ptr(zs),
-                 np_out, ptr(gamma), ptr(beta),
-                 ptr(sz) if want16 else None, N, H * W, cout, groups, W if pool else 0, None, 0)
-        if pool:
-            ARITH[("bn_relu", "with the 2x2 max-pool")] += 1
-        if want16 and np_out:
-            produced["p16"] = zs          # the next convolution's operand, produced here instead of by a separate pass
-        elif zs is not None:
-            produced["pbf"] = zs
-        if want16:
-            produced["scale"] = sz
-        _tap("fwd:y,stats", weight, y, stats)
-        ctx.save_for_backward(x0, x1, in_scale, weight, gamma, y, stats)
-        ctx.yshape = (N, H, W, cout)
-        ctx.pw, ctx.cfg, ctx.eval_mode, ctx.pool = pw, (groups, upsample, in_mode, first), False, pool
-        ctx.up4 = (not first) and up4
-        ctx.bias, ctx.beta, ctx.xs, ctx.sx, ctx.sx1 = bias, beta, xs, sx, sx1
-        ctx.opts = (_ASYNC["on"], _MASK_SKIP)       # the model's options when the node was made (rpnet_amd.schedule): backward reads these
-        return z
-
-    @staticmethod
-    def _eval_grad_tail(ctx, x0, x1, in_scale, weight, bias, gamma, beta, running_mean, running_var, y, z, pw, upsample, in_mode,
-                        first, out_split, produced, xs, sx, sx1, up4):
-        """eval mode with a gradient, behind the convolution that wrote y: stats [4][1][cout] = (scale, shift, running mean,
-        running invstd), z = relu(y scale + shift) with its measured maximum, the output's operand planes / fp16 scale from that
-        measurement (the running statistics give no a-priori bound), and what the backward needs"""
-        N, H, W, cout = y.shape
-        stats = _empty((4, 1, cout), y)
-        call("rpnet_bn_eval_affine", ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), BN_EPS, ptr(stats[0]),
-             ptr(stats[1]), cout)
-        stats[2, 0].copy_(running_mean)
-        torch.rsqrt(running_var + BN_EPS, out=stats[3, 0])
-        mx = torch.zeros(1, device=y.device, dtype=torch.float32)
-        call("rpnet_bn_eval_relu", ptr(y), ptr(stats[0]), ptr(stats[1]), ptr(z), ptr(mx), N * H * W, cout)
-        ARITH[("bn_relu", "eval mode, with a gradient")] += 1
-        if f16_mode() and cout % 32 == 0 and bool(out_split) and (_CORR16 or out_split != "corr"):
-            if out_split in (True, "corr"):
-                produced["p16"], produced["scale"] = split_f16(z, mx, a_is_bound=True)
-            else:
-                sz = torch.empty(1, device=y.device, dtype=torch.float32)
-                call("rpnet_pow2_scale", ptr(mx), ptr(sz))
-                produced["scale"] = sz
-        ctx.save_for_backward(x0, x1, in_scale, weight, gamma, y, stats)
-        ctx.yshape = (N, H, W, cout)
-        ctx.pw, ctx.cfg, ctx.eval_mode, ctx.pool, ctx.bn_eval = pw, (1, upsample, in_mode, first), False, False, True
-        ctx.up4 = up4
-        ctx.bias, ctx.beta, ctx.xs, ctx.sx, ctx.sx1 = bias, beta, xs, sx, sx1
-        ctx.opts = (_ASYNC["on"], _MASK_SKIP)
+            z, stats = _bn_eval_grad_output(y, gamma, beta, bnbuf, out_split, res)
+        _save_state(ctx, (x0, x1, in_scale, weight, gamma, y, stats), shape, groups, bias, beta, not training, res.pooled, pw, upsample,
+                    in_mode, plan)
         return z
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dz):
-        if ctx.eval_mode:
-            raise RuntimeError("rpnet_amd: an eval-mode layer made without a gradient-capable forward reached backward "
-                               "(conv_bn_relu_op decides from torch.is_grad_enabled() and requires_grad at call time)")
+        st = ctx.st
+        if st is None:
+            raise RuntimeError(_NO_BACKWARD)
         x0, x1, in_scale, weight, gamma, y, stats = ctx.saved_tensors
-        async_on, skip_on = getattr(ctx, "opts", (None, None))
-        pw = ctx.pw
-        groups, upsample, in_mode, first = ctx.cfg
+        pw = st.pw
+        N, H, W, cout = st.shape
         dz = dz.contiguous()
-        _tap("bwd_in:y,stats,dz", weight, y, stats, dz)
-        N, H, W, cout = ctx.yshape
-        wsb = query("rpnet_bn_workspace_bytes", cout, groups)
-        ws = _ws(wsb, dz)
-        beta, bias = ctx.beta, ctx.bias
-        if y is None:
-            # the first layer without its pre-BatchNorm tensor: reduction pass and weight gradient make y again from the image
-            direct = _direct(gamma, async_on) and _direct(beta, async_on)
-            dgamma, dbeta = (None, None) if direct else (_empty((cout,), dz), _empty((cout,), dz))
+        # which forms of dy the two consumers (wgrad, dgrad) want: split planes and / or fp32
+        np_ = st.xs[0].shape[0] if st.xs is not None else 0
+        need0, need1 = ctx.needs_input_grad[0], x1 is not None and ctx.needs_input_grad[1]
+        need_d = need0 or need1
+        wsplit = bool(np_) and pw.cin_pad % 64 == 0 and cout % 64 == 0 and x0.shape[-1] % 64 == 0
+        dsplit = bool(np_) and cout % 32 == 0 and need_d
+        if st.pool and (not (wsplit or dsplit) or dz.shape[1] * 2 != H):
+            raise RuntimeError("rpnet_amd: the pooled BatchNorm backward needs dy as split planes and the pooled gradient")
+        dy, dys, sdy, dgamma, dbeta, _ = _bn_backward(dz, y, stats, gamma, st.beta, st.shape, st.groups, st.async_on, st.bn_eval,
+                                                      np_ if (wsplit or dsplit) else 0, not wsplit or (need_d and not dsplit),
+                                                      W if st.pool else 0)
+        d, wgrad, wb = _wgrad_entry(st, x0, x1, in_scale, dy, dys, sdy, wsplit)
+        dyp = dys if wsplit else dy
+        dw, deferred = _schedule_wgrad(d, wgrad, wb, dyp, wsplit, weight, st.async_on,
+                                       (x0, x1, in_scale, dy, dyp, st.sx, st.sx1, sdy, st.xs))
+        dx0 = dx1 = dscale = None
+        if need_d:
+            need_s = in_scale is not None and ctx.needs_input_grad[2]   # soft_mask: the mask is differentiable
+            g0, g1, collapsed = _input_grad(st, dy, dys, sdy, x0, x1, None if need_s else in_scale, dsplit)
+        if deferred:      # behind this layer's dgrad (no input gradient wanted: no dgrad to wait for)
+            _release_wgrads(_WGRAD_DEFER - 1)
+        if need_d:
+            c0 = x0.shape[-1]
+            if need_s:   # d(x*f(s)) -> dx = g*f(s), ds = +-<g, x>
+                gx, dscale = torch.empty_like(g0), torch.empty_like(in_scale)
+                call("rpnet_rowdot_scale", ptr(g0), ptr(x0), ptr(in_scale), ptr(gx), ptr(dscale), N * H * W, c0, st.in_mode, 0)
+                g0 = gx
+            if st.upsample and not collapsed:
+                h0 = _empty(x0.shape, y)
+                call("rpnet_upsample2_bwd", ptr(g0), ptr(h0), N, H, W, c0)
+                g0 = h0
+            dx0 = g0 if need0 else None
+            dx1 = g1 if need1 else None
+        db = _bias_grad(st.bias, gamma, stats, dbeta, st.bn_eval, st.async_on)
+        return dx0, dx1, dscale, dw, db, dgamma, dbeta, None, None, None, None, None, None
+
+
+def _folded_eval_conv(x0, in_scale, bias, gamma, beta, bnbuf, pw, shape, upsample, in_mode, out_split, op0, op1, res):
+    """the inference path (eval mode under torch.no_grad): BatchNorm folded into the convolution's epilogue, one launch -> z.  f16x2 / f16: no a-priori
+    bound of the output, so the launch measures max |z| (out_absmax); the fp16 scale / planes follow from it or from the previous call's prediction."""
+    N, H, W, cout = shape
+    dev = x0.device
+    z = _empty(shape, x0)
+    scale, shift = _eval_affine(pw, gamma, beta, bnbuf, cout)
+    want16 = _want16(cout, out_split)
+    planes_out = out_split in (True, "corr")
+    mx = _absmax_slot(dev) if want16 else None
+    sp = pred_scale(dev) if want16 else None      # predicted scale of this launch (None: this call measures)
+    np_out = _MATH["planes"] if (planes_out and cout % 32 == 0 and not want16) else 0
+    zs = torch.empty((np_out, N, H, W, cout), device=dev, dtype=torch.bfloat16) if np_out else None
+    # up4 only where no planes are wanted of this launch ("scale" / False): its epilogue has affine, ReLU and maximum, but writes no planes
+    plan = _conv_plan(pw, op0, op1, in_scale, in_mode, upsample, N, H, W, cout, up4_allowed=not planes_out)
+    d = _conv_desc(plan, pw, bias, in_scale, in_mode, z, N, H, W, upsample, 1, scale, shift, 1)
+    d.y_split, d.split_out_planes, d.out_absmax = ptr(zs), np_out, ptr(mx)      # written by the epilogue: no separate split pass
+    z16 = None
+    if sp is not None and planes_out and plan.planes:
+        # the fp16 planes of output / predicted scale straight out of the epilogue: no second pass over z
+        fpo = _MATH["f16_planes"]
+        z16 = torch.empty((fpo, N, H, W, cout), device=dev, dtype=torch.float16)
+        d.y_split, d.split_out_planes, d.y_split_scale = ptr(z16), fpo, ptr(sp)
+    if plan.kind == "up4":
+        _cup4(d, 1)
+    else:
+        if _EVAL_SPLITK and d.split_planes == 2 and pw.taps == 9 and N * H * W * cout <= 128 * 256 * 64:
+            # a grid that would leave half of the CUs idle (batch-2 calls): lend the workspace for a split K range (splitk_ws)
+            nb = query("rpnet_conv_splitk_workspace_bytes", C.byref(d))
+            if nb:
+                d._ws = _ws(nb, x0)
+                d.splitk_ws, d.splitk_ws_bytes = ptr(d._ws), nb
+        _cconv("rpnet_conv_fwd", d)
+    res.pbf = zs
+    if want16:
+        _eval_out16(res, z, mx, sp, z16, out_split)
+    return z
+
+
+class Conv1BnRelu(Function):
+    """The first layer: Conv2d(1 -> cout, 3x3 p1, bias) -> BatchNorm2d -> ReLU on the image [N,H,W,1] (Conv1.conv.0), a direct convolution
+    (csrc/conv_first.hip): no packed weights, planes or GEMM; its backward may make the pre-BatchNorm tensor again from the image."""
+
+    @staticmethod
+    def forward(ctx, x0, weight, bias, gamma, beta, bnbuf, cfg, req, res):
+        """cfg = (training, groups, out_split); req / res: as for ConvBnRelu"""
+        hip.require_gpu(x0, weight)
+        training, groups, out_split = cfg
+        N, H, W, _ = x0.shape
+        cout = weight.shape[0]
+        shape = (N, H, W, cout)
+        if not training and not req.eval_grad:     # the inference path: BatchNorm folded into the launch (see _folded_eval_conv)
+            z = _empty(shape, x0)
+            scale, shift = _eval_affine(None, gamma, beta, bnbuf, cout)
+            want16 = _want16(cout, out_split)
+            mx = _absmax_slot(x0.device) if want16 else None
+            sp = pred_scale(x0.device) if want16 else None
+            call("rpnet_conv1_fwd", ptr(x0), ptr(weight), ptr(bias), ptr(z), ptr(scale), ptr(shift), N, H, W, cout, ptr(mx), None, 1)
+            if want16:
+                _eval_out16(res, z, mx, sp, None, out_split)
+            _save_state(ctx)
+            return z
+        if not training:
+            groups = 1       # running statistics: one affine for every image
+        # on fp16 planes whose only consumer reads the planes: y is summed, never written (see _CONV1_RECOMP)
+        recomp = bool(training and _CONV1_RECOMP and f16_mode() and cout % 8 == 0 and 256 % (cout // 8) == 0 and out_split is True
+                      and req.z_unused and not req.pool_req and _CONV1_BN_FUSE
+                      and query("rpnet_conv1_stats_blocks", N, H, W, cout, groups) > 0)
+        y = None if recomp else _empty(shape, x0)
+        # batch statistics out of the same launch (one partial row per block and group)
+        fused = query("rpnet_conv1_stats_blocks", N, H, W, cout, groups) if training else 0
+        part = torch.empty(groups * fused * cout * 2, device=x0.device, dtype=torch.float64) if fused else None
+        call("rpnet_conv1_fwd", ptr(x0), ptr(weight), ptr(bias), ptr(y), None, None, N, H, W, cout, None, ptr(part), groups)
+        if training:
+            stats = _bn_batch_stats(y, part, fused, shape, groups, gamma, beta, bnbuf)
+            z = _bn_output(y, stats, shape, groups, gamma, beta, out_split, req, res, False, (x0, weight, bias) if recomp else None)
+        else:
+            z, stats = _bn_eval_grad_output(y, gamma, beta, bnbuf, out_split, res)
+        _save_state(ctx, (x0, None, None, weight, gamma, y, stats), shape, groups, bias, beta, not training)
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz):
+        st = ctx.st
+        if st is None:
+            raise RuntimeError(_NO_BACKWARD)
+        x0, _, _, weight, gamma, y, stats = ctx.saved_tensors
+        N, H, W, cout = st.shape
+        groups, bias = st.groups, st.bias
+        dz = dz.contiguous()
+        part, rows = None, 0
+        if y is None:       # the reduction pass makes y again from the image
             rows = query("rpnet_conv1_bn_bwd_rows", N, H, W, cout, groups)
             part = torch.empty(groups * rows * cout * 2, device=dz.device, dtype=torch.float64)
             call("rpnet_conv1_bn_bwd_partial", ptr(x0), ptr(weight), ptr(bias), ptr(dz), ptr(stats), ptr(part), N, H, W, cout, groups)
-            ARITH[("bn_bwd", "first layer made again from the image")] += 1
-            if direct:
-                _order_wait(gamma.data_ptr())
-            call("rpnet_bn_bwd", ptr(dz), None, ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), None, None, 0,
-                 None, ptr(gamma.grad if direct else dgamma), ptr(beta.grad if direct else dbeta), N, H * W, cout, groups,
-                 1 if direct else 0, ptr(part), None, rows, 0, ptr(ws), wsb, None, 0)
-            if direct:
-                _order_done(gamma.data_ptr())
-            dw = torch.empty_like(weight)
-            wb = query("rpnet_conv1_wgrad_workspace_bytes", N, H, W, cout)
-            ws2 = _ws(wb, dz)
-            coef = ws.data_ptr() + query("rpnet_bn_bwd_coef_offset", cout, groups)
-            call("rpnet_conv1_wgrad_bn", ptr(x0), ptr(dz), None, ptr(stats), coef, ptr(dw), N, H, W, cout, groups, ptr(ws2), wb,
-                 ptr(weight), ptr(bias))
-            dw = _accumulate_direct(weight, dw, async_on)
-            dx0 = None
-            if ctx.needs_input_grad[0]:     # the image's gradient, y made again from the image as above
-                dx0 = _empty(x0.shape, dz)
-                call("rpnet_conv1_dgrad_bn", ptr(dz), None, ptr(stats), coef, ptr(weight), ptr(bias), ptr(x0), ptr(dx0), N, H, W, cout,
-                     groups)
-            db = None if _direct(bias, async_on) else torch.zeros_like(gamma)
-            return dx0, None, None, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None
-        # which forms of dy the two consumers (wgrad, dgrad) want: split-bf16 planes and / or fp32
-        np_ = ctx.xs[0].shape[0] if ctx.xs is not None else 0
-        need_d = not first and (ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]))
-        wsplit = bool(np_) and pw.cin_pad % 64 == 0 and cout % 64 == 0 and x0.shape[-1] % 64 == 0
-        dsplit = bool(np_) and cout % 32 == 0 and need_d
-        dys = torch.empty((np_,) + tuple(y.shape), device=y.device, dtype=torch.bfloat16) if (wsplit or dsplit) else None
-        sdy = torch.empty(1, device=y.device, dtype=torch.float32) if (dys is not None and np_ <= 2) else None   # fp16: tensor scale
-        dy = _empty(ctx.yshape, dz) if (first or not wsplit or (need_d and not dsplit)) else None
-        # Conv1.conv.0 (Cin = 1) has no input gradient: its direct weight gradient forms dy itself from dz, y and the
-        # coefficients of the reduction pass, so the apply pass (12 bytes per element of the largest tensor) is not run
-        fuse1 = first and _CONV1_BN_FUSE and stats.is_contiguous()
-        if fuse1:
-            dy = None
-        if ctx.pool and (dys is None or dz.shape[1] * 2 != H):
-            raise RuntimeError("rpnet_amd: the pooled BatchNorm backward needs dy as split planes and the pooled gradient")
-        bn_eval = getattr(ctx, "bn_eval", False)
-        # straight into the gradient bucket, no AccumulateGrad add (eval mode: the conv bias gradient is made from dbeta below)
-        direct = _direct(gamma, async_on) and _direct(beta, async_on) and not bn_eval
-        dgamma, dbeta = (None, None) if direct else (_empty((cout,), y), _empty((cout,), y))
-        ARITH[("bn_bwd", "eval mode" if bn_eval else "own reduction pass")] += 1
-        if direct:
-            _order_wait(gamma.data_ptr())  # gamma.grad / beta.grad: after the other chain's accumulation into them
-        if bn_eval:      # running statistics: dy = scale dz m, nothing subtracted; the coefficients in ws are zero
-            call("rpnet_bn_eval_bwd", ptr(dz), ptr(y), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(dy),
-                 ptr(dys), np_ if dys is not None else 0, ptr(sdy), ptr(dgamma), ptr(dbeta), N, H * W, cout, groups, 0,
-                 ptr(ws), wsb)
-        else:
-            call("rpnet_bn_bwd", ptr(dz), ptr(y), ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]),
-                 ptr(dy), ptr(dys), np_ if dys is not None else 0, ptr(sdy), ptr(gamma.grad if direct else dgamma),
-                 ptr(beta.grad if direct else dbeta), N, H * W, cout, groups, 1 if direct else 0, None, None, 0,
-                 W if ctx.pool else 0, ptr(ws), wsb, None, 0)
-        if direct:
-            _order_done(gamma.data_ptr())
-        _tap("bn_bwd:dz,dy,dys,sdy,ws", weight, dz, dy, dys, sdy, ws)
+        # the direct weight / image gradients form dy themselves from dz, y and the reduction's coefficients: no apply pass (12 B / element)
+        fuse = y is None or (_CONV1_BN_FUSE and stats.is_contiguous())
+        dy, _, _, dgamma, dbeta, ws = _bn_backward(dz, y, stats, gamma, st.beta, st.shape, groups, st.async_on, st.bn_eval,
+                                                   want_dy=not fuse, part=part, rows=rows)
         dw = torch.empty_like(weight)
-        dx0 = dx1 = dscale = None
-        if first:
-            wb = query("rpnet_conv1_wgrad_workspace_bytes", N, H, W, cout)
-            ws2 = _ws(wb, y)
-            coef = ws.data_ptr() + query("rpnet_bn_bwd_coef_offset", cout, groups)
-            if fuse1:
-                call("rpnet_conv1_wgrad_bn", ptr(x0), ptr(dz), ptr(y), ptr(stats), coef, ptr(dw), N, H, W, cout, groups,
-                     ptr(ws2), wb, None, None)
-            else:
-                call("rpnet_conv1_wgrad", ptr(x0), ptr(dy), ptr(dw), N, H, W, cout, ptr(ws2), wb)
-            dw = _accumulate_direct(weight, dw, async_on)
-            if ctx.needs_input_grad[0]:
-                # the image's gradient (saliency, robustness checks): dy formed on the spot from dz, y and the coefficients of
-                # the reduction pass (zero in eval mode), so no fp32 dy is needed for it
-                dx0 = _empty(x0.shape, dz)
-                call("rpnet_conv1_dgrad_bn", ptr(dz), ptr(y), ptr(stats), coef, ptr(weight), None, None, ptr(dx0), N, H, W, cout,
-                     groups)
+        wb = query("rpnet_conv1_wgrad_workspace_bytes", N, H, W, cout)
+        ws2 = _ws(wb, dz)
+        coef = ws.data_ptr() + query("rpnet_bn_bwd_coef_offset", cout, groups)
+        again = (ptr(weight), ptr(bias)) if y is None else (None, None)      # what makes y again where it was not kept
+        if fuse:
+            call("rpnet_conv1_wgrad_bn", ptr(x0), ptr(dz), ptr(y), ptr(stats), coef, ptr(dw), N, H, W, cout, groups, ptr(ws2), wb, *again)
         else:
-            # same gather descriptor as the forward (sources, up-sampling, x*mask factor); dy is the other operand
-            if wsplit:       # both wgrad operands as split planes (the x*mask factor is already in xs)
-                dyp = dys
-                d = _desc(ctx.xs[0], ctx.xs[1], None, None, None, 0, None, None, N, H, W, pw.taps, upsample,
-                          co_split=(cout, 0), wgrad=True)
-                d.split_planes = np_
-                if np_ <= 2:
-                    d.acc_scale_x, d.acc_scale_dy, d.acc_scale_x1 = ptr(ctx.sx), ptr(sdy), ptr(ctx.sx1)
-            else:
-                dyp = dy
-                d = _desc(x0, x1, None, None, in_scale, in_mode, dy, None, N, H, W, pw.taps, upsample, wgrad=True)
-            wb = query("rpnet_conv_wgrad_workspace_bytes", N, H, W, pw.cin_pad, cout, pw.taps)
-            # the collapsed up_conv (see _UP4): sixteen tap products per source pixel instead of thirty-six
-            wup4 = bool(getattr(ctx, "up4", False)) and wsplit and np_ in (1, 2) and bool(query("rpnet_conv_wgrad_up4_supported", C.byref(d)))
-            if wup4:
-                wb = query("rpnet_conv_wgrad_up4_workspace_bytes", N, H, W, pw.cin, cout)
-
-            def wgrad(dy_ptr, dw_ptr, ws_t):
-                """the weight-gradient entry point of this layer: GEMM phase (dw_ptr None), reduce phase (dy_ptr None) or both"""
-                if wup4:
-                    if dy_ptr is not None:
-                        ARITH[("wgrad3x3_up4", _PLANE_NAME[d.split_planes])] += 1
-                    call("rpnet_conv_wgrad_up4", C.byref(d), dy_ptr, dw_ptr, ptr(ws_t), wb)
-                else:
-                    _cconv("rpnet_conv_wgrad", d, dy_ptr, dw_ptr, pw.cin, pw.off0, pw.split, pw.off1, ptr(ws_t), wb)
-            deferred = None
-            if _direct(weight, async_on):
-                # the stream this backward node runs on (the one that produced dy and will run this layer's dgrad), taken NOW:
-                # a deferred launch may be released by a later node that runs on another stream (the CRE's second branch, the
-                # encoder's second chain), and must still wait for THIS one
-                prod = torch.cuda.current_stream(y.device)
-
-                def launch_async():
-                    dev = y.device
-                    side, main = _side_stream(dev), prod
-                    side.wait_stream(main)                   # dy, x are ready on the producing stream (deferred: and the dgrad is done)
-                    d.accumulate = 1
-                    with torch.cuda.stream(side):
-                        ws2 = _ws(wb, y)
-                        if wsplit:   # GEMM on the side stream, its HBM-bound reduce on a third one under the next layer's GEMM
-                            wgrad(ptr(dyp), None, ws2)
-                            red = _reduce_stream(dev)
-                            red.wait_stream(side)
-                            _ASYNC["keep"].append(ws2)      # read by the reduce; alive until join_side_streams
-                            with torch.cuda.stream(red):
-                                wgrad(None, ptr(weight.grad), ws2)
-                        else:
-                            wgrad(ptr(dyp), ptr(weight.grad), ws2)
-                    # alive until join_side_streams (the saved tensors outlive this node anyway)
-                    _ASYNC["keep"].append((x0, x1, in_scale, dy, dyp, ctx.sx, ctx.sx1, sdy, ctx.xs))
-                    if not _ASYNC["queued"]:      # once per backward pass (reset_async re-arms it after a failed one)
-                        torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-                        _ASYNC["queued"] = True
-                    _ASYNC["pending"].add(dev)
-                # _WGRAD_DEFER >= 1 (default 1): the launch goes out right BEHIND this layer's dgrad and waits for it, so that it
-                # starts when the main chain enters the BatchNorm-backward passes of the layer below — every HBM-bound pass
-                # of the chain then has an MFMA-bound partner on the machine.  Launched in front of the dgrad (=0) the two
-                # GEMMs share the CUs, end together, and the passes behind them run alone.
-                if _WGRAD_DEFER:
-                    _defer_wgrad(launch_async)
-                    deferred = True
-                else:
-                    launch_async()
-                dw = None
-            else:
-                ws2 = _ws(wb, y)
-                wgrad(ptr(dyp), ptr(dw), ws2)
-            need0 = ctx.needs_input_grad[0]
-            need1 = x1 is not None and ctx.needs_input_grad[1]
-            if need0 or need1:
-                c0, c1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-                # dgrad = the same implicit GEMM on dy with the flipped/transposed weight pack
-                need_s = in_scale is not None and ctx.needs_input_grad[2]   # soft_mask: the mask is differentiable
-                up4 = bool(getattr(ctx, "up4", False)) and dsplit and np_ in (1, 2)
-                if up4:
-                    # the collapsed up_conv: the input gradient comes out at the SOURCE resolution (the 2 x 2 sum is in the launch)
-                    pk4 = pw.up4_packs(np_)
-                    g0, g1 = _empty(x0.shape, y), None
-                    dd = _desc(dys, None, pk4[1], None, None, 0, g0, None, N, H, W, pw.taps, 1)
-                    dd.split_planes = np_
-                    dd.acc_scale_col, dd.acc_scale_x = ptr(pk4[3]), ptr(sdy)
-                    up4 = bool(query("rpnet_conv_up4_supported", C.byref(dd), 2))
-                if not up4:
-                    g0 = _empty((N, H, W, c0), y)
-                    g1 = _empty((N, H, W, c1), y) if x1 is not None else None
-                if up4:
-                    pass
-                elif dsplit:
-                    pk = pw.split_packs(np_)
-                    dd = _desc(dys, None, pk[1], None, None, 0, g0, g1, N, H, W,
-                               pw.taps, 0, out_scale=None if need_s else in_scale, out_mode=in_mode)
-                    dd.split_planes = np_
-                    if np_ <= 2:
-                        dd.acc_scale_col, dd.acc_scale_x = ptr(pk[3]), ptr(sdy)
-                        if pw.taps == 9 and x1 is None and not upsample and not need_s:
-                            _set_skip(dd, in_scale, in_mode, 0, N, H, W, skip_on)
-                else:
-                    dd = _desc(dy, None, pw.wd, None, None, 0, g0, g1, N, H, W, pw.taps, 0,
-                               out_scale=None if need_s else in_scale, out_mode=in_mode)
-                if up4:
-                    _cup4(dd, 2)
-                else:
-                    _cconv("rpnet_conv_fwd", dd)
-                _tap("dgrad:g0,g1", weight, g0, g1)
-                if deferred:
-                    _release_wgrads(_WGRAD_DEFER - 1)
-                    deferred = None
-                if need_s:   # d(x*f(s)) -> dx = g*f(s), ds = +-<g, x>
-                    gx, dscale = torch.empty_like(g0), torch.empty_like(in_scale)
-                    call("rpnet_rowdot_scale", ptr(g0), ptr(x0), ptr(in_scale), ptr(gx), ptr(dscale), N * H * W, c0,
-                         in_mode, 0)
-                    g0 = gx
-                if upsample and not up4:
-                    h0 = _empty(x0.shape, y)
-                    call("rpnet_upsample2_bwd", ptr(g0), ptr(h0), N, H, W, c0)
-                    g0 = h0
-                dx0 = g0 if need0 else None
-                dx1 = g1 if need1 else None
-            if deferred:                  # no input gradient wanted: no dgrad to wait for
-                _release_wgrads(_WGRAD_DEFER - 1)
-        if bn_eval:      # eval mode: d(bias) = sum over pixels of dy = scale dbeta (the running statistics do not absorb it)
-            db = _accumulate_direct(bias, stats[0, 0] * dbeta, async_on)
-        else:            # conv bias in front of a train-mode BatchNorm: the gradient is analytically zero
-            db = None if _direct(bias, async_on) else torch.zeros_like(gamma)
-        return dx0, dx1, dscale, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None
+            call("rpnet_conv1_wgrad", ptr(x0), ptr(dy), ptr(dw), N, H, W, cout, ptr(ws2), wb)
+        dw = _accumulate_direct(weight, dw, st.async_on)
+        dx0 = None
+        if ctx.needs_input_grad[0]:
+            # the image's gradient (saliency, robustness checks): dy formed on the spot as above (eval mode: zero coefficients)
+            dx0 = _empty(x0.shape, dz)
+            call("rpnet_conv1_dgrad_bn", ptr(dz), ptr(y), ptr(stats), coef, ptr(weight), again[1], ptr(x0) if y is None else None,
+                 ptr(dx0), N, H, W, cout, groups)
+        db = _bias_grad(bias, gamma, stats, dbeta, st.bn_eval, st.async_on)
+        return dx0, dw, db, dgamma, dbeta, None, None, None, None
 
 
 def conv_bn_relu_op(x0, conv, bn, cache, training, x1=None, in_scale=None, in_mode=0, groups=1, upsample=False, split=None,
@@ -1404,22 +1410,26 @@ def conv_bn_relu_op(x0, conv, bn, cache, training, x1=None, in_scale=None, in_mo
     and its `deferred` = (y, batch scale, batch shift); the consumer's fused launch applies them and fills the tensor
     (CosineMatchUp over cre.q's output: the refinement loop's glue, rpnet_refine_glue_fwd)."""
     op0, op1 = as_operand(x0), as_operand(x1)
-    pw = cache.get(conv.weight, split) if (conv.weight.shape[1] >= 32 or split is not None) else None
-    produced = {"z_unused": bool(z_unused) and training and conv.weight.shape[0] % 64 == 0,
-                "pool": bool(pool) and training and _POOL_FUSE, "pool_req": bool(pool),
-                "defer_act": bool(defer_act) and training and not out_split}
-    if not training and torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (op0.x, None if op1 is None else op1.x, in_scale, conv.weight, conv.bias,
-                                                        bn.weight, bn.bias)):
-        # eval mode with a gradient (test-time fine-tuning with frozen statistics, image gradients): the gradient-capable form
-        # of the forward (ConvBnRelu._eval_grad_tail); under torch.no_grad the folded form of the inference path runs
-        produced["eval_grad"] = True
-    z = ConvBnRelu.apply(op0.x, None if op1 is None else op1.x, in_scale, conv.weight, conv.bias, bn.weight, bn.bias,
-                         bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None, pw, training, groups,
-                         1 if upsample else 0, in_mode, out_split, (op0, op1), produced)
-    out = Operand(z, produced.get("p16"), produced.get("pbf"), produced.get("scale"), bool(produced.get("planes_only")),
-                  produced.get("deferred"))
-    if pool and not produced.get("pooled"):
+    w = conv.weight
+    x1t = None if op1 is None else op1.x
+    # eval mode with a gradient (test-time fine-tuning with frozen statistics, image gradients): the gradient-capable form of the
+    # forward (_bn_eval_grad_output); under torch.no_grad the folded form of the inference path runs
+    eval_grad = not training and torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (op0.x, x1t, in_scale, w, conv.bias, bn.weight, bn.bias))
+    req = _Req(bool(z_unused) and training and w.shape[0] % 64 == 0, bool(pool) and training and _POOL_FUSE, bool(pool),
+               bool(defer_act) and training and not out_split, eval_grad)
+    res = _Produced()
+    bnbuf = (bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None)
+    if w.shape[1] == 1 and w.shape[2] == 3:      # Cin = 1: the direct convolution
+        if x1t is not None or in_scale is not None or upsample:
+            raise RuntimeError("rpnet_amd: the first-layer convolution takes one plain source (no second source, mask or up-sampling)")
+        z = Conv1BnRelu.apply(op0.x, w, conv.bias, bn.weight, bn.bias, bnbuf, (training, groups, out_split), req, res)
+    else:
+        pw = cache.get(w, split)
+        z = ConvBnRelu.apply(op0.x, x1t, in_scale, w, conv.bias, bn.weight, bn.bias, bnbuf, pw,
+                             (training, groups, 1 if upsample else 0, in_mode, out_split), (op0, op1), req, res)
+    out = Operand(z, res.p16, res.pbf, res.scale, res.planes_only, res.deferred)
+    if pool and not res.pooled:
         out = maxpool2(out)
     return out
 
@@ -1439,18 +1449,13 @@ class ConvRelu(Function):
         N, H, W, _ = x.shape
         cout = weight.shape[0]
         z = _empty((N, H, W, cout), x)
-        xs = None
-        if _use_split(pw, x, None):
-            np_ = _MATH["planes"]
-            xs = split_bf16(x, np_)
-            d = _desc(xs, None, pw.split_packs(np_)[0], bias, None, 0, z, None, N, H, W, pw.taps, 0, ep_relu=1 if relu else 0)
-            d.split_planes = np_
-        else:
-            d = _desc(x, None, pw.wp, bias, None, 0, z, None, N, H, W, pw.taps, 0, ep_relu=1 if relu else 0)
+        # a bare tensor carries no bound: three bf16 planes in every split mode (or fp32), never fp16 planes or the up4 form
+        plan = _conv_plan(pw, Operand(x), None, None, 0, 0, N, H, W, cout)
+        d = _conv_desc(plan, pw, bias, None, 0, z, N, H, W, 0, ep_relu=1 if relu else 0)
         d.dilation = dilation
         _cconv("rpnet_conv_fwd", d)
         ctx.save_for_backward(x, weight, z)
-        ctx.pw, ctx.cfg, ctx.xs = pw, (relu, dilation), xs
+        ctx.pw, ctx.cfg, ctx.xs = pw, (relu, dilation), plan.xs[0] if plan.planes else None
         return z
 
     @staticmethod
@@ -1463,8 +1468,7 @@ class ConvRelu(Function):
         dy, db = torch.empty_like(z), _empty((cout,), z)
         wb = query("rpnet_bias_relu_bwd_workspace_bytes", cout)
         ws = _ws(wb, z)
-        call("rpnet_bias_relu_bwd", ptr(dz.contiguous()), ptr(z) if relu else None, ptr(dy), ptr(db), N * H * W, cout,
-             ptr(ws), wb)
+        call("rpnet_bias_relu_bwd", ptr(dz.contiguous()), ptr(z) if relu else None, ptr(dy), ptr(db), N * H * W, cout, ptr(ws), wb)
         dw = torch.empty_like(weight)
         dys = split_bf16(dy, xs.shape[0]) if xs is not None and cout % 32 == 0 else None
         if dys is not None and dilation <= 1 and pw.cin % 64 == 0 and cout % 64 == 0:
@@ -1480,11 +1484,7 @@ class ConvRelu(Function):
         dx = None
         if ctx.needs_input_grad[0] and pw.has_wd:
             dx = _empty(x.shape, z)
-            if dys is not None:
-                dd = _desc(dys, None, pw.split_packs(xs.shape[0])[1], None, None, 0, dx, None, N, H, W, pw.taps, 0)
-                dd.split_planes = xs.shape[0]
-            else:
-                dd = _desc(dy, None, pw.wd, None, None, 0, dx, None, N, H, W, pw.taps, 0)
+            dd = _dgrad_desc(pw, dys, None, dy, dx, None, N, H, W)
             dd.dilation = dilation
             _cconv("rpnet_conv_fwd", dd)
         return dx, dw, db, None, None, None
@@ -1699,7 +1699,7 @@ class LocalCorr(Function):
             np_ = f1s.shape[0]          # 2, or 1 in "f16" mode
             ARITH[("corr", _PLANE_NAME[np_])] += 1
             # the correlation has no a-priori bound: the launch measures max |corr|, its planes are scaled by that
-            mx = _absmax_slot(f1.device) if (produced is not None and _CONV1X1_SPLIT) else None
+            mx = _absmax_slot(f1.device) if produced is not None else None
             # eval mode on predicted scales (pred_scale: the previous call's maximum of this very launch x 4): the kernel writes the
             # correlation's planes itself; otherwise (training, a measuring call) a split pass on the measured bound
             sp = pred_scale(f1.device) if (mx is not None and _CORR_PRED_PLANES) else None

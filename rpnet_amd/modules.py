@@ -343,7 +343,7 @@ class ContextCorrelationEncoder(nn.Module):
         # fm1 / fm2 feed the correlation and (fm1) the 1x1 convolution, both of which read fp16 planes in f16x2 / f16
         # training: their fp32 form is then never written (RF.conv_bn_relu_op(z_unused); a consumer that wanted the
         # values would raise)
-        zu = _ZSKIP and sp == "corr" and RF._CORR16 and RF._CONV1X1_SPLIT and self.w_k[0].weight.shape[0] % 128 == 0
+        zu = _ZSKIP and sp == "corr" and self.w_k[0].weight.shape[0] % 128 == 0
 
         mk, mq = ((mask, 1, pre[0]), (mask, 2, pre[1])) if (pre is not None and mask is not None) else (None, None)
 
