@@ -1,0 +1,209 @@
+"""Evaluation of a data set with the items assembled on the device.
+
+`DeviceEvalSource.item(idx)` reproduces `FewshotRegReader(mode="eval")[idx]` (rpnet_amd/utils/volume_reader.py) — the support
+volume choice with the same consumption of the `random` generator, the k-block pairing of every query slice with a support slice,
+the registration pre-step — but keeps the preprocessed volumes in HBM (the host reader decodes and preprocesses both NRRD volumes
+for every item) and builds the item there: one table of S slice numbers goes up, ONE launch (`rpnet_eval_item_gather`,
+csrc/evalitem.hip) writes the tensors the model takes and the two [0,1] planes the registration takes, and the registration
+launches (rpnet_amd/registration.py) run without their copies to the host.  After `warm()` an item makes no device-to-host copy and
+no host synchronisation.
+
+`evaluate_dataset` walks the items: item -> `VolumeSegmenter(..., counts_out=table[j])` -> `rpnet_ncc_pairs` into `ncc[j]`.  The Dice
+tallies of all items live in one int64 table and the image similarity figures in one fp64 table; both cross to the host ONCE, after
+the last item, and the lines of tools/eval_driver.py:evaluate are printed from them.
+"""
+import os
+import random
+from collections import defaultdict
+
+import numpy as np
+import torch
+
+from . import augment as A
+from . import hip
+from . import registration as R
+from .hip import call, ptr
+from .utils.volume_reader import FewshotVolumeReader
+from .volume import VolumeSegmenter, dice_from_counts
+
+
+def eval_slice_table(n_support, n_query, k):
+    """The pairing of FewshotSliceReader's eval branch (one shot) as a table: (k_effective, support_slice int32[n_query]) —
+    query slice s is matched with support slice support_slice[s], the slice at the centre of the support volume's block j for every
+    query slice of block j.  The numpy expressions are the host reader's own (`s_pick`, `q_edge`, `k = min(k, depths)`), so they round
+    as it does.  For a few (depth, k) pairs `np.arange(0, nq, nq / k)` yields k + 1 block edges and the reader's loop over k blocks
+    stops short of the last query slices (7 support / 17 query slices, k = 7: 14 of 17); the table then has as many entries as the
+    loop pairs, and DeviceEvalSource refuses the item."""
+    k = min([k, n_support, n_query])
+    n = n_support
+    s_pick = np.floor(np.arange(n / k / 2, n, n / k)).astype(np.int32)
+    nq = n_query
+    q_edge = np.floor(np.array(np.arange(0, nq, nq / k).tolist() + [nq])).astype(np.int32)
+    counts = [int(q_edge[j + 1] - q_edge[j]) for j in range(k)]
+    return k, np.repeat(s_pick[:k], counts).astype(np.int32)
+
+
+def _volume(x, what):
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous float32 [D,H,W] tensor, got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def eval_item_gather(s_img, s_msk, q_img, q_msk, support_slice):
+    """One `rpnet_eval_item_gather` launch.  s_img, s_msk [Ds,H,W] and q_img, q_msk [S,H,W]: float32 volumes on the GPU;
+    support_slice: S slice numbers in HOST memory (numpy or a CPU tensor), checked against [0, Ds) here, before the upload (the
+    kernel cannot refuse a table it reads on the device).  Returns (support image, support label, query image, query label, support
+    in [0,1], query in [0,1]), each [S,H,W]."""
+    hip.require_gpu(s_img, s_msk, q_img, q_msk)
+    s_img, s_msk, q_img, q_msk = (_volume(s_img, "support image"), _volume(s_msk, "support mask"), _volume(q_img, "query image"),
+                                  _volume(q_msk, "query mask"))
+    if s_img.shape != s_msk.shape or q_img.shape != q_msk.shape:
+        raise ValueError(f"image and mask differ: support {tuple(s_img.shape)} / {tuple(s_msk.shape)}, query {tuple(q_img.shape)} / {tuple(q_msk.shape)}")
+    if s_img.shape[1:] != q_img.shape[1:]:
+        raise NotImplementedError(f"support {tuple(s_img.shape[1:])} and query {tuple(q_img.shape[1:])} slices differ in size")
+    if torch.is_tensor(support_slice) and support_slice.is_cuda:
+        raise TypeError("eval_item_gather: the slice table must be in host memory (it is checked before it is uploaded)")
+    table = np.ascontiguousarray(np.asarray(support_slice), dtype=np.int32).reshape(-1)
+    (Ds, H, W), S = s_img.shape, q_img.shape[0]
+    if table.shape[0] != S:
+        raise ValueError(f"eval_item_gather: {table.shape[0]} table entries for {S} query slices")
+    if S and (int(table.min()) < 0 or int(table.max()) >= Ds):
+        raise ValueError(f"eval_item_gather: slice table entries {int(table.min())} .. {int(table.max())} outside the support volume's [0, {Ds})")
+    dev_table = A.upload(torch.from_numpy(table), q_img.device)
+    outs = [torch.empty((S, H, W), device=q_img.device, dtype=torch.float32) for _ in range(6)]
+    call("rpnet_eval_item_gather", ptr(s_img), ptr(s_msk), ptr(q_img), ptr(q_msk), ptr(dev_table), *[ptr(t) for t in outs], Ds, S, H, W)
+    return tuple(outs)
+
+
+def ncc_pairs(query, warped, affine, table, row):
+    """table[row] = (NCC(query, warped), NCC(query, affine)) — net.registration.NCC over whole tensors, in fp64, bit-identical from run
+    to run (csrc/evalitem.hip).  query, warped, affine: contiguous float32 GPU tensors of one element count; table: float64 [n,2] on
+    the GPU.  Three launches, nothing copied."""
+    hip.require_gpu(query, warped, affine, table)
+    n = query.numel()
+    for t, what in ((query, "query"), (warped, "warped"), (affine, "affine")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"ncc_pairs: {what} must be a contiguous float32 tensor of {n} elements, got {t.dtype} {tuple(t.shape)}")
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 2 or not table.is_contiguous():
+        raise ValueError(f"ncc_pairs: the table must be a contiguous float64 [n,2] tensor, got {table.dtype} {tuple(table.shape)}")
+    wb = hip.query("rpnet_ncc_pairs_workspace_bytes", n)
+    ws = torch.empty((max(wb, 8),), device=query.device, dtype=torch.uint8)
+    call("rpnet_ncc_pairs", ptr(query), ptr(warped), ptr(affine), n, ptr(table), int(row), table.shape[0], ptr(ws), wb)
+
+
+class DeviceEvalSource:
+    """config: the keys of FewshotVolumeReader / FewshotSliceReader (class_csv_dir, eval_classes, k, do_deformable, crop_size, ...);
+    one way, one shot (`test_shot` 1), `use_registration_loss: True` and no `use_registration_mask` (what tools/eval_driver.py runs).
+    cache_volumes=False reloads a volume every time it is used.  `k` sticks across items, as in the host reader."""
+
+    def __init__(self, data_dir, set_name, config, device, cache_volumes=True):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceEvalSource runs on MI355X only (there is no CPU fallback; the host reader is "
+                               "rpnet_amd.utils.volume_reader.FewshotRegReader)")
+        if config["n_way"] != 1 or config["n_shot"] != 1:
+            raise NotImplementedError("one way, one shot (the slice reader asserts one way)")
+        if config.get("test_shot", config["n_shot"]) > 1:
+            raise NotImplementedError("DeviceEvalSource pairs every query slice with ONE support slice: test_shot > 1 is not supported "
+                                      "(the host reader rpnet_amd.utils.volume_reader.FewshotRegReader serves it)")
+        if config.get("use_registration_mask", False):
+            raise NotImplementedError("DeviceEvalSource does not build the mask channels of use_registration_mask "
+                                      "(the host reader rpnet_amd.utils.volume_reader.FewshotRegReader serves them)")
+        if not config.get("use_registration_loss", False):
+            raise TypeError("DeviceEvalSource needs use_registration_loss: True, like FewshotRegReader")
+        self.cfg, self.k = config, config["k"]
+        self.reader = FewshotVolumeReader(data_dir, set_name, config, mode="eval")
+        self.cache_volumes, self._volumes = cache_volumes, {}
+        self.pre = None               # the last item's gathered tensors before registration and its slice table
+
+    def __len__(self):
+        return len(self.reader)
+
+    def volume(self, c, i):
+        """(image [D,H,W], mask [D,H,W]) float32 on the device: the reader's deterministic preprocessing, once"""
+        if (c, i) in self._volumes:
+            return self._volumes[(c, i)]
+        s = self.reader.load_image_and_mask(self.reader.data_info[c][i]["pid"], self.reader.classes[c])
+        v = (torch.from_numpy(s["image"][0]).to(self.device), torch.from_numpy(s["mask"][0]).to(self.device))
+        if self.cache_volumes:
+            self._volumes[(c, i)] = v
+        return v
+
+    def warm(self):
+        """load every volume and the small constants of the registration (its base grids and, with do_deformable, its smoothing
+        kernel), so that no later item copies anything up with a blocking copy"""
+        for c, i in self.reader.indices:
+            img = self.volume(c, i)[0]
+            R.base_grid(img.shape[2], img.device), R.base_grid(img.shape[1], img.device)
+            if self.cfg.get("do_deformable", True):
+                R._device_kernel((2.0, 2.0), img.device)            # the key demons_register looks up
+
+    def item(self, idx):
+        rd, cfg = self.reader, self.cfg
+        c, qv = rd.indices[idx]
+        others = [i for i in range(rd.n_data[c]) if i != qv]
+        (s,) = random.choices(others, k=1)                      # the one draw of the host item (eval mode has no elastic coin)
+        s_img, s_msk = self.volume(c, s)
+        q_img, q_msk = self.volume(c, qv)
+        if s_img.shape[1:] != q_img.shape[1:]:
+            # make_support_query_same_size would pad here; load_image_and_mask leaves every volume at crop_size, so it never does
+            raise NotImplementedError(f"support {tuple(s_img.shape[1:])} and query {tuple(q_img.shape[1:])} slices differ in size")
+        self.k, table = eval_slice_table(s_img.shape[0], q_img.shape[0], self.k)       # k sticks for later items
+        if table.shape[0] != q_img.shape[0]:
+            raise ValueError(f"the reader's k-block loop pairs {table.shape[0]} of {q_img.shape[0]} query slices (support depth "
+                             f"{s_img.shape[0]}, k = {self.k}): its block edges round to k + 1 blocks, and the host item is ragged too")
+        sup, sup_l, q, lab, sup01, q01 = eval_item_gather(s_img, s_msk, q_img, q_msk, table)
+        self.pre = {"support_images": sup[:, None], "support_labels": sup_l, "query_images": q[:, None], "query_labels": lab,
+                    "support_slices": table}
+        field, reg_pred, warped_src, aff_pred, aff_src = R.register_slices(sup01, q01, sup_l, do_deformable=cfg.get("do_deformable", True))
+        # reg_pred is already 0 / 1 (thresholded at 0.1 by the warp): the host's `> 0.5` changes nothing
+        return {"support_images": [[aff_src[:, None]]], "support_labels": [[aff_pred]], "query_images": q[:, None], "query_labels": lab,
+                "appr_query_labels": reg_pred, "warped_supp": warped_src, "class_id": c, "pid": rd.data_info[c][qv]["pid"],
+                "supp_pids": [(c, s)], "registration_field": field}
+
+
+def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None):
+    """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
+    test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
+    The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
+    one fp64 table [n_items, 2]; both are copied to the host once, after the last item.  save_pred: a directory that receives every
+    volume's mask as <pid>_<class>.nrrd (the masks stay on the device until the tables have crossed).  out: a dict that receives the
+    host tables as out["counts"] and out["ncc"]."""
+    from .utils import nrrd
+    seg = VolumeSegmenter(net, batch=batch, graphed=graphed)
+    classes = config["eval_classes"]
+    n = len(source) if n_items is None else min(n_items, len(source))
+    dev = next(net.parameters()).device
+    T, K = net.num_iter, 2
+    table = torch.zeros((n, T + 2, K - 1, 3), device=dev, dtype=torch.int64)
+    ncc = torch.zeros((n, 2), device=dev, dtype=torch.float64)
+    meta, masks = [], []
+    for j in range(n):
+        s = source.item(j)
+        res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j])
+        ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
+        meta.append((s["pid"], classes[s["class_id"]]))
+        if save_pred:
+            masks.append(res.mask)
+    counts, ncc = table.cpu().numpy(), ncc.cpu().numpy()          # the two transfers of the data set
+    if out is not None:
+        out["counts"], out["ncc"] = counts, ncc
+    dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
+    if save_pred:
+        os.makedirs(save_pred, exist_ok=True)
+    for j, (pid, name) in enumerate(meta):
+        d_aff, d_few = dice_from_counts(counts[j, T + 1])[0], dice_from_counts(counts[j, T])[0]
+        dsc_affine[name].append(d_aff)
+        dsc_fewshot[name].append(d_few)
+        line = f"{j} {pid} affine ({ncc[j, 0]:.4f}, {ncc[j, 1]:.4f}) {d_aff}, fewshot {d_few}"
+        for k in range(T):
+            d = dice_from_counts(counts[j, k])[0]
+            dsc_ref[name][k].append(d)
+            line += f" ref {k} {d},"
+        print(line)
+        if save_pred:
+            nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
+    for name in classes:
+        if dsc_fewshot[name]:
+            print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}")
+    return dsc_affine, dsc_fewshot, dsc_ref

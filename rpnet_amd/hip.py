@@ -136,6 +136,16 @@ _SIGS = {
 ABI_SYMBOLS = tuple(_SIGS)
 ABI_VERSION = 111     # RPNET_ABI_VERSION of include/rpnet_abi.h
 
+# the evaluation-item entry points: include/rpnet_eval_abi.h (additions beside rpnet_abi.h; their ledger is tests/eval_abi_ledger.py)
+_EVAL_SIGS = {
+    "rpnet_eval_abi_version": (ci, []),
+    "rpnet_eval_item_gather": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "rpnet_ncc_pairs_workspace_bytes": (cs, [cs]),
+    "rpnet_ncc_pairs": (ci, [vp, vp, vp, cs, vp, ci, ci, vp, cs, vp]),
+}
+EVAL_ABI_SYMBOLS = tuple(_EVAL_SIGS)
+EVAL_ABI_VERSION = 1     # RPNET_EVAL_ABI_VERSION of include/rpnet_eval_abi.h
+
 
 def lib_path():
     return _LIB_PATH
@@ -153,9 +163,14 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)
+        for name, (res, args) in list(_SIGS.items()) + list(_EVAL_SIGS.items()):
+            fn = getattr(lib, name, None)
+            if fn is None:
+                raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
             fn.restype, fn.argtypes = res, args
+        if lib.rpnet_eval_abi_version() != EVAL_ABI_VERSION:
+            raise RuntimeError(f"{_LIB_PATH} has evaluation-item ABI version {lib.rpnet_eval_abi_version()}, this binding was written for "
+                               f"{EVAL_ABI_VERSION} (include/rpnet_eval_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

@@ -67,9 +67,19 @@ def seg_tally(sources, kinds, n_valid, labels=None, counts=None, mask=None, mask
              mask_src, N, K, H, W)
 
 
+def check_counts_out(counts_out, K, T=None):
+    """the tally table a caller hands to VolumeSegmenter: a contiguous int64 tensor [T+2, K-1, 3] (T is checked where it is known)"""
+    if not torch.is_tensor(counts_out) or counts_out.dtype != torch.int64 or not counts_out.is_contiguous():
+        raise ValueError("counts_out must be a contiguous int64 tensor [T+2, K-1, 3]")
+    if counts_out.dim() != 3 or tuple(counts_out.shape[1:]) != (K - 1, 3) or (T is not None and counts_out.shape[0] != T + 2):
+        rows = "T+2" if T is None else str(T + 2)
+        raise ValueError(f"counts_out must have the shape [{rows}, {K - 1}, 3] (refinement 0 .. T-1, output, affine baseline), "
+                         f"got {tuple(counts_out.shape)}")
+
+
 class VolumeSegmenter:
-    """`VolumeSegmenter(net, batch=8, graphed=True)(support_images, support_fg, query_images, appr_query_labels, query_labels=None)`
-    -> VolumeResult(mask, counts, dice).
+    """`VolumeSegmenter(net, batch=8, graphed=True)(support_images, support_fg, query_images, appr_query_labels, query_labels=None,
+    counts_out=None)` -> VolumeResult(mask, counts, dice).
 
     Arguments are the volume-level tensors of a `FewshotRegReader` eval item: nested lists `[way][shot]` of support images
     [S,1,H,W] and foreground masks [S,H,W] (background = 1 - foreground), query images [S,1,H,W], the approximate (affine) labels
@@ -82,7 +92,10 @@ class VolumeSegmenter:
     tallies and the mask.  graphed and 1-way 1-shot: the calls go through GraphedEval — `graphed=True`: the one wrapper all
     VolumeSegmenters of this net share (`graphed_eval(net)`), or pass your own `GraphedEval(net)` to use that; a net must not get a
     second wrapper while graphs of the first are in use (graph.py clears the net's weight packs) — otherwise eager `net(...)`.  The
-    only device-to-host transfer this class adds is the counter table, once per volume."""
+    only device-to-host transfer this class adds is the counter table, once per volume.
+      counts_out  an int64 tensor [T+2, K-1, 3] on the net's device (needs query_labels): the tallies are ADDED to it, nothing crosses
+                  to the host, and `counts` and `dice` of the result are None — for a caller that keeps the tables of many volumes
+                  on the device and fetches them once (rpnet_amd.dataset_eval.evaluate_dataset)."""
 
     def __init__(self, net, batch=8, graphed=True):
         if batch < 1:
@@ -121,12 +134,18 @@ class VolumeSegmenter:
         tab[0][len(tab[2])] = appr.data_ptr()
         return tab
 
-    def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None):
+    def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None):
         dev = next(self.net.parameters()).device
         n_ways, n_shots = len(support_images), len(support_images[0])
         S, B = query_images.shape[0], self.batch
         H, W = query_images.shape[-2:]
         K = n_ways + 1
+        if counts_out is not None:
+            if query_labels is None:
+                raise ValueError("counts_out needs query_labels (there is nothing to tally without the ground truth)")
+            check_counts_out(counts_out, K, getattr(self.net, "num_iter", None))
+            if counts_out.device != dev:
+                raise ValueError(f"counts_out is on {counts_out.device}, the net on {dev}")
         nb = -(-S // B)
         pad = nb * B - S
 
@@ -156,14 +175,16 @@ class VolumeSegmenter:
                 tab = self._table(out, appr[sl], tuple(si[0][0][sl].shape))
                 T = len(tab[2]) - 1
                 if labels is not None and counts is None:
-                    counts = torch.zeros((T + 2, K - 1, 3), device=dev, dtype=torch.int64)
+                    if counts_out is not None:
+                        check_counts_out(counts_out, K, T)
+                    counts = counts_out if counts_out is not None else torch.zeros((T + 2, K - 1, 3), device=dev, dtype=torch.int64)
                 n_valid = min(B, S - i * B)
                 if n_valid != nv_now:
                     self._nv.fill_(n_valid)
                     nv_now = n_valid
                 seg_tally(tab[2] + [appr[sl]], [0] * (T + 1) + [1], self._nv, labels[sl] if labels is not None else None, counts,
                           mask[sl], mask_src=T, K=K, _table=tab)
-        if counts is None:
+        if counts is None or counts_out is not None:
             return VolumeResult(mask[:S], None, None)
         host = counts.cpu().numpy()                 # the one transfer of the volume
         T = host.shape[0] - 2

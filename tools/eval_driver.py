@@ -4,11 +4,14 @@
 iteration), using only the symbols that driver imports, at the reference's import paths.
 The reference file itself cannot run offline (it needs tensorboard and the private data).
 
-    python tools/eval_driver.py --yaml yamls/example.yml [--items 2] [--on-device] [--batch 8] [--save-pred DIR]
+    python tools/eval_driver.py --yaml yamls/example.yml [--items 2] [--on-device] [--device-items] [--batch 8] [--save-pred DIR]
 
 --on-device: the same lines from rpnet_amd.volume.VolumeSegmenter (masks and Dice tallies on the device, one transfer per volume,
 `--batch` slices per model call through the captured graph); --save-pred DIR writes each volume's predicted mask as
-DIR/<pid>_<class>.nrrd (uint8, gzip) and implies --on-device.
+DIR/<pid>_<class>.nrrd (uint8, gzip) and implies --on-device.  --device-items (implies --on-device; needs NRRD volumes under the
+yaml's data_dir): the items too are built on the device (rpnet_amd.dataset_eval.DeviceEvalSource: volumes cached in HBM, one gather
+launch and the registration launches per item) and the tallies and both image similarity figures of all volumes cross to the host
+once, after the last volume (rpnet_amd.dataset_eval.evaluate_dataset).
 """
 import argparse
 import os
@@ -105,17 +108,24 @@ def main():
     ap.add_argument("--on-device", action="store_true", help="masks and Dice tallies on the device (rpnet_amd.volume.VolumeSegmenter)")
     ap.add_argument("--batch", type=int, default=None, help="slices per model call (default: 2, or 8 with --on-device)")
     ap.add_argument("--save-pred", default=None, metavar="DIR", help="write each volume's mask as DIR/<pid>_<class>.nrrd; implies --on-device")
+    ap.add_argument("--device-items", action="store_true",
+                    help="build the items on the device too and fetch all tallies once (rpnet_amd.dataset_eval); implies --on-device")
     a = ap.parse_args()
     config, args = load_yaml(a.yaml)
     config["n_iter_refinement"] = config["n_test_iter_refinement"]            # test_rpnet.py:51
-    loader = FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
+    loader = None if a.device_items else FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
     net = model_factory[args.net](pretrained_path=config.get("pretrained_path"),
                                   cfg={"align": True, "backbone": config.get("backbone", "vgg")}, backbone_cfg=config).cuda()
     if args.ckpt:
         state = net.state_dict()
         state.update(torch.load(args.ckpt)["state_dict"])
         net.load_state_dict(state)
-    if a.on_device or a.save_pred:
+    if a.device_items:
+        from rpnet_amd.dataset_eval import DeviceEvalSource, evaluate_dataset
+        source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device)
+        source.warm()
+        evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred)
+    elif a.on_device or a.save_pred:
         evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred)
     else:
         evaluate(net, loader, config, a.items, a.batch or 2)
