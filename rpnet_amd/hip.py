@@ -146,6 +146,17 @@ _EVAL_SIGS = {
 EVAL_ABI_SYMBOLS = tuple(_EVAL_SIGS)
 EVAL_ABI_VERSION = 1     # RPNET_EVAL_ABI_VERSION of include/rpnet_eval_abi.h
 
+# the optimizer entry points: include/rpnet_optim_abi.h (additions beside the two headers above; their ledger is tests/optim_abi_ledger.py)
+i64p = C.POINTER(C.c_int64)
+_OPTIM_SIGS = {
+    "rpnet_optim_abi_version": (ci, []),
+    "rpnet_adam_plan_bytes": (cs, [i64p, ci]),
+    "rpnet_adam_plan": (ci, [C.POINTER(vp), i64p, i64p, ci, vp, cs, i64p]),
+    "rpnet_adam_step": (ci, [vp, C.c_int64, vp, vp, vp, vp, vp]),
+}
+OPTIM_ABI_SYMBOLS = tuple(_OPTIM_SIGS)
+OPTIM_ABI_VERSION = 1     # RPNET_OPTIM_ABI_VERSION of include/rpnet_optim_abi.h
+
 
 def lib_path():
     return _LIB_PATH
@@ -163,7 +174,7 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        for name, (res, args) in list(_SIGS.items()) + list(_EVAL_SIGS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
@@ -171,6 +182,9 @@ def load():
         if lib.rpnet_eval_abi_version() != EVAL_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has evaluation-item ABI version {lib.rpnet_eval_abi_version()}, this binding was written for "
                                f"{EVAL_ABI_VERSION} (include/rpnet_eval_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
+        if lib.rpnet_optim_abi_version() != OPTIM_ABI_VERSION:
+            raise RuntimeError(f"{_LIB_PATH} has optimizer ABI version {lib.rpnet_optim_abi_version()}, this binding was written for "
+                               f"{OPTIM_ABI_VERSION} (include/rpnet_optim_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

@@ -119,8 +119,16 @@ class FlatGradBucket:
         self._tail_work = None
         self.flat.zero_()
 
-    def allreduce(self, async_op=False):
-        """sum over ranks, then 1/world (mean gradient).  No-op without a process group."""
+    @property
+    def mean_scale(self):
+        """what allreduce(average=True) multiplies the summed gradients by: 1 / world under a process group, 1.0 without one.
+        The consumer of allreduce(average=False) applies it itself (rpnet_amd.optim.FusedAdam(grad_scale=bucket.mean_scale))."""
+        return 1.0 / dist.get_world_size() if self._active() else 1.0
+
+    def allreduce(self, async_op=False, average=True):
+        """sum over ranks, then 1/world (mean gradient).  No-op without a process group.
+        average=False leaves the SUM in the bucket and saves the pass over it: the consumer applies 1/world itself
+        (rpnet_amd.optim.FusedAdam(grad_scale=bucket.mean_scale))."""
         from .functional import join_side_streams
         join_side_streams()          # also in single-process runs: the optimizer step reads the bucket next
         if not self._active():
@@ -135,6 +143,8 @@ class FlatGradBucket:
             w.wait()
         self._work = {}
         self._tail_work = None
+        if not average:
+            return None
         self.flat.mul_(1.0 / dist.get_world_size())
         return None
 

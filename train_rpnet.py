@@ -53,8 +53,10 @@ def episode(seed, batch, size, dev):
 
 
 def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, seed=0, steps_per_epoch=50, n_ways=1, n_shots=1,
-          source=None):
-    """source: a rpnet_amd.episodes.DeviceEpisodeSource; its batch(batch) replaces the synthetic episodes (`size` is then
+          source=None, optimizer="torch"):
+    """optimizer: "torch" (torch.optim.Adam, the default) or "fused" (rpnet_amd.optim.FusedAdam: the update as one HIP launch over
+    the bucket, the 1/world of the gradient mean folded into it).
+    source: a rpnet_amd.episodes.DeviceEpisodeSource; its batch(batch) replaces the synthetic episodes (`size` is then
     whatever the volumes' crop_size gives)"""
     rank = dist.get_rank() if dist.is_initialized() else 0
     net = model_factory[config.get("net", "RP_Net")](pretrained_path=config.get("pretrained_path"),
@@ -68,8 +70,15 @@ def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, 
     caller_stream = None
     if torch.device(dev).type == "cuda":
         caller_stream = torch.cuda.current_stream(dev)
+    if optimizer not in ("torch", "fused"):
+        raise ValueError(f"optimizer {optimizer!r}: 'torch' or 'fused'")
     params = [p for _, p in bucket.params]
-    opt = torch.optim.Adam(params, lr=lr if lr is not None else config["init_lr"], weight_decay=config["weight_decay"])
+    if optimizer == "fused":
+        from rpnet_amd.optim import FusedAdam
+        opt = FusedAdam(bucket, lr=lr if lr is not None else config["init_lr"], weight_decay=config["weight_decay"],
+                        grad_scale=bucket.mean_scale)
+    else:
+        opt = torch.optim.Adam(params, lr=lr if lr is not None else config["init_lr"], weight_decay=config["weight_decay"])
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=config["scheduler_step"])
     scaler = config["align_loss_scaler"]
     history, t0 = [], time.time()
@@ -97,7 +106,10 @@ def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, 
         out = net(si, fg, bg, qi, appr_query_labels=appr)
         loss = objective(out, ql, scaler)
         RF.backward(loss)                   # (cached gradient seed)
-        bucket.allreduce()
+        if optimizer == "fused":
+            bucket.allreduce(average=False)     # the sum: FusedAdam applies 1/world inside the update
+        else:
+            bucket.allreduce()
         opt.step()
         history.append(loss.detach())       # no host sync per step
         if (it + 1) % steps_per_epoch == 0:
@@ -127,6 +139,8 @@ def main():
     ap.add_argument("--data_dir", default=None, help="directory of <pid>_clean.nrrd / <pid>_<roi>.nrrd volumes: train on them "
                     "(episodes assembled on the device) instead of synthetic episodes; needs --set_name")
     ap.add_argument("--set_name", default=None, help=".csv / .npy list of the training pids (with --data_dir)")
+    ap.add_argument("--optimizer", choices=("torch", "fused"), default="torch", help="torch: torch.optim.Adam (default); fused: "
+                    "rpnet_amd.optim.FusedAdam, the Adam update as one HIP launch over the flat gradient bucket")
     a = ap.parse_args()
     if (a.data_dir is None) != (a.set_name is None):
         ap.error("--data_dir and --set_name come together")
@@ -156,7 +170,7 @@ def main():
         from rpnet_amd.episodes import DeviceEpisodeSource
         source = DeviceEpisodeSource(a.data_dir, a.set_name, config, dev, rank=int(os.environ.get("RANK", "0")), world=world)
     train(config, a.steps, a.batch or config["batch_size"], a.size, dev, lr=a.lr, out_dir=a.out_dir or config.get("out_dir"),
-          source=source)
+          source=source, optimizer=a.optimizer)
     if world > 1:
         dist.destroy_process_group()
 
