@@ -157,6 +157,17 @@ _OPTIM_SIGS = {
 OPTIM_ABI_SYMBOLS = tuple(_OPTIM_SIGS)
 OPTIM_ABI_VERSION = 1     # RPNET_OPTIM_ABI_VERSION of include/rpnet_optim_abi.h
 
+# the gradient guard of the optimizer step: include/rpnet_guard_abi.h (additions beside the three headers above; their ledger is
+# tests/guard_abi_ledger.py)
+_GUARD_SIGS = {
+    "rpnet_guard_abi_version": (ci, []),
+    "rpnet_grad_guard_init": (ci, [vp, cd, ci, C.c_int64]),
+    "rpnet_grad_sumsq": (ci, [vp, C.c_int64, vp, vp, vp, vp, vp]),
+    "rpnet_adam_step_guarded": (ci, [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+GUARD_ABI_SYMBOLS = tuple(_GUARD_SIGS)
+GUARD_ABI_VERSION = 1     # RPNET_GUARD_ABI_VERSION of include/rpnet_guard_abi.h
+
 
 def lib_path():
     return _LIB_PATH
@@ -174,7 +185,7 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        for name, (res, args) in list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()) + list(_GUARD_SIGS.items()):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
@@ -185,6 +196,9 @@ def load():
         if lib.rpnet_optim_abi_version() != OPTIM_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has optimizer ABI version {lib.rpnet_optim_abi_version()}, this binding was written for "
                                f"{OPTIM_ABI_VERSION} (include/rpnet_optim_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
+        if lib.rpnet_guard_abi_version() != GUARD_ABI_VERSION:
+            raise RuntimeError(f"{_LIB_PATH} has gradient-guard ABI version {lib.rpnet_guard_abi_version()}, this binding was written for "
+                               f"{GUARD_ABI_VERSION} (include/rpnet_guard_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

@@ -6,8 +6,13 @@ two launches with nothing read back: replayable in a captured graph.
 
 The semantics are torch.optim.Adam(amsgrad=False, maximize=False) with L2 weight decay, in fp32, and the state dict is Adam's
 (state[i] = {step, exp_avg, exp_avg_sq} + param_groups): a run begun under either optimizer resumes under the other.
+
+The gradient guard (include/rpnet_guard_abi.h): FusedAdam(max_grad_norm=, skip_nonfinite=, history=) puts the gradient's 2-norm
+(fp64, one more read of the bucket), torch.nn.utils.clip_grad_norm_'s coefficient and the decision to skip a step whose gradient
+holds an inf or a NaN in front of the update, all in device memory: three launches, still nothing read back.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -17,6 +22,48 @@ from . import hip
 _HYPER_FIELDS = ("lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale")      # struct rpnet_adam_hyper: six doubles,
 _HYPER_STEP = 6                                                                    # the int64 step, ten floats: 96 bytes
 _HYPER_WORDS = 12
+# struct rpnet_grad_guard as ten 8-byte words: max_norm, skip_nonfinite, history_capacity | sumsq, norm, coef, (coef_f, skip), attempt,
+_GUARD_WORDS = 10                                                                  # skipped, clipped: 80 bytes
+_G_NORM, _G_COEF, _G_PAIR, _G_ATTEMPT, _G_SKIPPED, _G_CLIPPED = 4, 5, 6, 7, 8, 9
+_HISTORY_ROW = 3                                                                   # RPNET_GUARD_HISTORY_ROW: norm, coef, skip
+
+
+def clip_coefficient(norm, max_norm):
+    """the factor a gradient of 2-norm `norm` is multiplied by under the threshold `max_norm`: c = max_norm / (norm + 1e-6), c when
+    c <= 1 or c is NaN, else 1.  This is torch.nn.utils.clip_grad_norm_'s formula with its constant, and what the guarded step
+    forms in fp64 on the device.  Host only, Python floats."""
+    norm, max_norm = float(norm), float(max_norm)
+    try:
+        c = max_norm / (norm + 1e-6)
+    except ZeroDivisionError:               # norm == -1e-6 cannot come from a norm; keep the function total
+        c = math.inf
+    return 1.0 if c > 1.0 else c
+
+
+def _check_guard_args(max_grad_norm, skip_nonfinite, history):
+    """-> (the guard's max_norm, skip_nonfinite, history) as float, bool, int, or ValueError / TypeError; no GPU call"""
+    if max_grad_norm is None:
+        max_norm = math.inf
+    else:
+        max_norm = float(max_grad_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"FusedAdam: max_grad_norm={max_grad_norm!r} (a threshold above 0, or None for no clipping)")
+    if not isinstance(skip_nonfinite, (bool, int)):
+        raise TypeError(f"FusedAdam: skip_nonfinite={skip_nonfinite!r} (True or False)")
+    if isinstance(history, bool) or not isinstance(history, int):
+        raise TypeError(f"FusedAdam: history={history!r} (the number of attempts the ring keeps, an int)")
+    if history < 0:
+        raise ValueError(f"FusedAdam: history={history} (0 for no ring)")
+    return max_norm, bool(skip_nonfinite), history
+
+
+def guard_block(max_norm, skip_nonfinite, history):
+    """rpnet_grad_guard_init: struct rpnet_grad_guard for these settings as a float64 tensor of ten words on the host"""
+    host = torch.zeros(_GUARD_WORDS, dtype=torch.float64)
+    rc = hip.query("rpnet_grad_guard_init", host.data_ptr(), float(max_norm), int(bool(skip_nonfinite)), int(history))
+    if rc != 0:
+        raise ValueError(f"rpnet_grad_guard_init failed (rc={rc}): {hip.query('rpnet_last_error_string').decode()}")
+    return host
 
 
 def plan_chunks(ptrs, counts, offsets):
@@ -48,9 +95,25 @@ class FusedAdam(torch.optim.Optimizer):
     p.data = ...).  The learning rate is read from param_groups[0]["lr"] at every step and uploaded when it changed (8 bytes from
     pinned memory, nothing when it did not), which is what lr_scheduler.StepLR needs; the other hyper-parameters are uploaded at
     construction and by load_state_dict().  step() can be captured with torch.cuda.graph: upload a changed learning rate with
-    sync_lr() between replays."""
+    sync_lr() between replays.
 
-    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    max_grad_norm, skip_nonfinite, history: the gradient guard.  With the defaults (None, False, 0) step() is the two launches above
+    and nothing is allocated for the guard.  With any of them set, step() is rpnet_adam_step_guarded, three launches:
+      * the 2-norm of grad_scale * g over the whole bucket, summed in fp64 in a fixed order;
+      * max_grad_norm: the gradient the update sees is clip_coefficient(norm, max_grad_norm) * (grad_scale * g), the result of
+        flat.mul_(grad_scale) followed by torch.nn.utils.clip_grad_norm_(params, max_grad_norm).  Unlike clip_grad_norm_ the bucket
+        is NOT rewritten: bucket.flat and every p.grad hold the unclipped gradient after the step;
+      * skip_nonfinite: when the sum of squares is inf or NaN the step is not taken: p, exp_avg, exp_avg_sq and the step count stay
+        as they are and guard_stats()["skipped"] goes up by one.  Without it such a gradient goes the way it goes through
+        clip_grad_norm_(error_if_nonfinite=False): a NaN norm makes every parameter NaN;
+      * history: a ring in device memory that keeps (norm, coef, skip) of the last `history` attempts, for guard_stats().
+    Neither is a param-group key: state_dict() stays torch.optim.Adam's, the counters are not saved and start at zero after a resume.
+    step_count() counts steps TAKEN.  A captured guarded step replays like the plain one; set_max_grad_norm() between replays.
+    Data-parallel: behind bucket.allreduce(average=False) every rank holds the same sum, hence the same norm and the same decision."""
+
+    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, max_grad_norm=None,
+                 skip_nonfinite=False, history=0):
+        max_norm, skip_nonfinite, history = _check_guard_args(max_grad_norm, skip_nonfinite, history)
         params = [p for _, p in bucket.params]
         hip.require_gpu(bucket.flat, *params)
         if not (0.0 <= lr and 0.0 <= eps and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and 0.0 <= weight_decay):
@@ -86,6 +149,16 @@ class FusedAdam(torch.optim.Optimizer):
         self._lr_event = None
         self._lr_uploaded = None
         self._upload_hyper(step=0)
+        self.guarded = max_grad_norm is not None or skip_nonfinite or history > 0
+        self.max_grad_norm, self.skip_nonfinite, self.history = max_norm, skip_nonfinite, history
+        self.partials = self.guard = self.ring = None            # the guard's buffers: made once, here or never
+        self._probe = None                                       # grad_norm()'s own partial sums and guard block
+        self._max_norm_host = self._max_norm_event = None
+        if self.guarded:
+            self.partials = torch.empty(self.n_chunks, dtype=torch.float64, device=flat.device)
+            self.guard = guard_block(max_norm, skip_nonfinite, history).to(flat.device)
+            self.ring = torch.zeros(history * _HISTORY_ROW, dtype=torch.float64, device=flat.device) if history else None
+            self._max_norm_host = torch.zeros(1, dtype=torch.float64).pin_memory()
 
     # ------------------------------------------------------------------------------------------------ the device block
     def _upload_hyper(self, step):
@@ -120,6 +193,54 @@ class FusedAdam(torch.optim.Optimizer):
         """steps taken so far, read from the device (synchronises)"""
         return int(self.hyper.view(torch.int64)[_HYPER_STEP].item())
 
+    # ------------------------------------------------------------------------------------------------ the guard
+    def set_max_grad_norm(self, max_grad_norm):
+        """a new clip threshold (None: no clipping) for an optimizer built with the guard: 8 bytes from pinned memory; between
+        two replays of a captured step it takes effect without a recapture, inside a capture it is refused"""
+        max_norm = _check_guard_args(max_grad_norm, False, 0)[0]
+        if not self.guarded:
+            raise RuntimeError("FusedAdam: built without the gradient guard (max_grad_norm=None, skip_nonfinite=False, history=0); "
+                               "its step has no threshold to set")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdam: set_max_grad_norm() inside a graph capture: call it before the capture and between replays")
+        if self._max_norm_event is not None:
+            self._max_norm_event.synchronize()
+        self._max_norm_host[0] = max_norm
+        self.guard[0:1].copy_(self._max_norm_host, non_blocking=True)
+        self._max_norm_event = torch.cuda.Event()
+        self._max_norm_event.record()
+        self.max_grad_norm = max_norm
+
+    def guard_stats(self):
+        """what the guard holds, read from the device (synchronises): norm, coef and skip of the last attempt, the counters
+        attempt / skipped / clipped, and history: [(norm, coef, skip), ...] of the last min(attempt, history) attempts, oldest first"""
+        if not self.guarded:
+            raise RuntimeError("FusedAdam: built without the gradient guard")
+        host = self.guard.cpu()
+        words = host.view(torch.int64)
+        attempt = int(words[_G_ATTEMPT])
+        out = {"norm": float(host[_G_NORM]), "coef": float(host[_G_COEF]), "skip": int(host.view(torch.int32)[2 * _G_PAIR + 1]),
+               "attempt": attempt, "skipped": int(words[_G_SKIPPED]), "clipped": int(words[_G_CLIPPED]), "history": []}
+        if self.ring is not None:
+            rows = self.ring.cpu().view(self.history, _HISTORY_ROW)
+            for a in range(max(0, attempt - self.history), attempt):
+                norm, coef, skip = rows[a % self.history].tolist()
+                out["history"].append((norm, coef, int(skip)))
+        return out
+
+    def grad_norm(self):
+        """the 2-norm of grad_scale * bucket.flat as the guard forms it (rpnet_grad_sumsq alone: two launches, fp64, nothing read
+        back) -> a 0-dim float64 tensor on the device.  Works without the guard too; its buffers are grad_norm()'s own, so the
+        counters and the ring of guard_stats() see steps only."""
+        if self._probe is None:
+            flat = self.bucket.flat
+            self._probe = (torch.empty(self.n_chunks, dtype=torch.float64, device=flat.device),
+                           guard_block(math.inf, False, 0).to(flat.device))
+        partials, guard = self._probe
+        hip.call("rpnet_grad_sumsq", hip.ptr(self.table), self.n_chunks, hip.ptr(self.bucket.flat), hip.ptr(partials), hip.ptr(guard),
+                 None)
+        return guard[_G_NORM] * abs(self.grad_scale)
+
     # ------------------------------------------------------------------------------------------------ the step
     @torch.no_grad()
     def step(self, closure=None):
@@ -130,8 +251,12 @@ class FusedAdam(torch.optim.Optimizer):
                 raise RuntimeError(f"FusedAdam: parameter {n} has moved since the chunk table was planned (net.to(...) or an "
                                    "assignment to .data): build a new FlatGradBucket and FusedAdam")
         self.sync_lr()
-        hip.call("rpnet_adam_step", hip.ptr(self.table), self.n_chunks, hip.ptr(self.bucket.flat), hip.ptr(self.exp_avg),
-                 hip.ptr(self.exp_avg_sq), hip.ptr(self.hyper))
+        if self.guarded:
+            hip.call("rpnet_adam_step_guarded", hip.ptr(self.table), self.n_chunks, hip.ptr(self.bucket.flat), hip.ptr(self.exp_avg),
+                     hip.ptr(self.exp_avg_sq), hip.ptr(self.hyper), hip.ptr(self.partials), hip.ptr(self.guard), hip.ptr(self.ring))
+        else:
+            hip.call("rpnet_adam_step", hip.ptr(self.table), self.n_chunks, hip.ptr(self.bucket.flat), hip.ptr(self.exp_avg),
+                     hip.ptr(self.exp_avg_sq), hip.ptr(self.hyper))
         return None
 
     def zero_grad(self, set_to_none=False):

@@ -1,12 +1,14 @@
 """The optimizer step on the real model's gradient bucket: torch.optim.Adam against rpnet_amd.optim.FusedAdam, and the two passes
-over the bucket that stand beside it (flat.mul_ of the gradient mean, the bucket's memset).
+over the bucket that stand beside it (flat.mul_ of the gradient mean, the bucket's memset); then the gradient guard: the norm
+launch pair alone (rpnet_grad_sumsq), a guarded step (FusedAdam(max_grad_norm=, skip_nonfinite=True): three launches) and what it
+replaces, torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam.step().
 
     python tools/bench_optim.py [--rounds 7] [--iters 20] [--out profiles/optim_step.txt] [--label TEXT] [--append]
 
 One process, one GPU.  Each figure is a device-event time over `iters` back-to-back calls (no host wait inside the window), taken
-`rounds` times with the four candidates alternating inside every round; reported: the median per call, min and max over the rounds,
+`rounds` times with the candidates alternating inside every round; reported: the median per call, min and max over the rounds,
 and the effective bandwidth.  The update is counted at 28 bytes per element (read g, p, m, v; write p, m, v), flat.mul_ at 8, the
-memset at 4, beside the 6.29 TB/s of a float4 copy on this chip.  --label names the library build (its chunk size) in the output;
+memset at 4, the norm at 4 (one read of g), the guarded step at 32 (the norm's read and the update), beside the 6.29 TB/s of a float4 copy on this chip.  --label names the library build (its chunk size) in the output;
 --append adds to the file instead of replacing it.
 """
 import argparse
@@ -52,11 +54,28 @@ net_f, bucket_f = model()
 opt_f = FusedAdam(bucket_f, lr=cfg["init_lr"], weight_decay=cfg["weight_decay"])
 n = bucket_f.numel
 scratch = torch.randn(n, device=dev)
+# the guard: a threshold at half the gradient's norm, so that the guarded step and clip_grad_norm_ both really clip
+net_g, bucket_g = model()
+half = 0.5 * float(bucket_g.flat.double().norm())
+opt_g = FusedAdam(bucket_g, lr=cfg["init_lr"], weight_decay=cfg["weight_decay"], max_grad_norm=half, skip_nonfinite=True)
+net_c, bucket_c = model()
+params_c = [p for _, p in bucket_c.params]
+opt_c = torch.optim.Adam(params_c, lr=cfg["init_lr"], weight_decay=cfg["weight_decay"])
+
+
+def clip_and_adam():
+    torch.nn.utils.clip_grad_norm_(params_c, half)          # rewrites the bucket (it multiplies whatever the coefficient is)
+    opt_c.step()
+
+
 cands = {
     "torch.optim.Adam.step()": (opt_t.step, 28),
     "FusedAdam.step()": (opt_f.step, 28),
     "flat.mul_(1 / world)": (lambda: scratch.mul_(0.5), 8),
     "bucket memset (flat.zero_())": (lambda: scratch.zero_(), 4),
+    "rpnet_grad_sumsq (grad_norm())": (opt_f.grad_norm, 4),
+    "FusedAdam.step() guarded": (opt_g.step, 32),
+    "clip_grad_norm_ + Adam.step()": (clip_and_adam, 32),
 }
 
 
@@ -93,6 +112,11 @@ for k, (_, bpe) in cands.items():
                  f"-> {n * bpe / med[k] / 1e3:7.1f} GB/s = {n * bpe / med[k] / 1e6 / COPY_TBS * 100:5.1f} % of the copy rate")
 lines.append(f"  torch / fused = {med['torch.optim.Adam.step()'] / med['FusedAdam.step()']:.2f} x; {n * 28 / 1e6:.0f} MB at the copy rate "
              f"would take {n * 28 / COPY_TBS / 1e6:.0f} us")
+gs = opt_g.guard_stats()
+lines.append(f"  guarded / plain FusedAdam = {med['FusedAdam.step() guarded'] / med['FusedAdam.step()']:.2f} x "
+             f"(+{med['FusedAdam.step() guarded'] - med['FusedAdam.step()']:.1f} us); clip_grad_norm_ + Adam / guarded = "
+             f"{med['clip_grad_norm_ + Adam.step()'] / med['FusedAdam.step() guarded']:.2f} x; the guard saw norm {gs['norm']:.6g}, "
+             f"coef {gs['coef']:.4f}, {gs['clipped']} of {gs['attempt']} steps clipped, {gs['skipped']} skipped")
 lines.append(f"  largest |p_torch - p_fused| after the same {5 + args.rounds * args.iters} steps on the same gradient: {drift:.3e}")
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "a" if args.append else "w") as f:

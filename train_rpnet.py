@@ -53,11 +53,26 @@ def episode(seed, batch, size, dev):
 
 
 def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, seed=0, steps_per_epoch=50, n_ways=1, n_shots=1,
-          source=None, optimizer="torch"):
+          source=None, optimizer="torch", clip_grad_norm=None, skip_nonfinite=False, stats=None):
     """optimizer: "torch" (torch.optim.Adam, the default) or "fused" (rpnet_amd.optim.FusedAdam: the update as one HIP launch over
     the bucket, the 1/world of the gradient mean folded into it).
+    clip_grad_norm: clip the 2-norm of the (mean) gradient of the bucket's parameters to this value; None: off.  Under "fused" it is
+    FusedAdam(max_grad_norm=...): norm, coefficient and update on the device, nothing read back.  Under "torch" it is
+    torch.nn.utils.clip_grad_norm_(params, clip_grad_norm) between the all-reduce and the step, so that the two are comparable.
+    skip_nonfinite: do not take a step whose gradient holds an inf or a NaN ("fused" only: under "torch" the decision would need a
+    host read every step, so it is refused).  Data-parallel runs need no extra collective for either: behind
+    allreduce(average=False) every rank holds the same sum, so every rank forms the same norm and takes the same decision.
+    With either on, the log line (which synchronises anyway) carries the last gradient norm and the number of skipped steps.
+    stats: a dict that receives the optimizer under "optimizer" (FusedAdam.guard_stats() and .grad_norm() for the caller).
     source: a rpnet_amd.episodes.DeviceEpisodeSource; its batch(batch) replaces the synthetic episodes (`size` is then
     whatever the volumes' crop_size gives)"""
+    if optimizer not in ("torch", "fused"):
+        raise ValueError(f"optimizer {optimizer!r}: 'torch' or 'fused'")
+    if optimizer == "torch" and skip_nonfinite:
+        raise ValueError("skip_nonfinite needs optimizer='fused': under torch.optim.Adam the decision would take a host read of the "
+                         "gradient norm at every step")
+    if clip_grad_norm is not None and not float(clip_grad_norm) > 0.0:
+        raise ValueError(f"clip_grad_norm {clip_grad_norm!r}: a threshold above 0")
     rank = dist.get_rank() if dist.is_initialized() else 0
     net = model_factory[config.get("net", "RP_Net")](pretrained_path=config.get("pretrained_path"),
                                                     cfg={"align": True, "backbone": config.get("backbone", "UNet")},
@@ -70,17 +85,19 @@ def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, 
     caller_stream = None
     if torch.device(dev).type == "cuda":
         caller_stream = torch.cuda.current_stream(dev)
-    if optimizer not in ("torch", "fused"):
-        raise ValueError(f"optimizer {optimizer!r}: 'torch' or 'fused'")
     params = [p for _, p in bucket.params]
+    guarded = clip_grad_norm is not None or skip_nonfinite
     if optimizer == "fused":
-        from rpnet_amd.optim import FusedAdam
+        from rpnet_amd.optim import FusedAdam            # (None, False: the unguarded step, two launches)
         opt = FusedAdam(bucket, lr=lr if lr is not None else config["init_lr"], weight_decay=config["weight_decay"],
-                        grad_scale=bucket.mean_scale)
+                        grad_scale=bucket.mean_scale, max_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
     else:
         opt = torch.optim.Adam(params, lr=lr if lr is not None else config["init_lr"], weight_decay=config["weight_decay"])
+    if stats is not None:
+        stats["optimizer"] = opt
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=config["scheduler_step"])
     scaler = config["align_loss_scaler"]
+    gnorm = None                         # under "torch": the norm clip_grad_norm_ returned last, a device tensor
     history, t0 = [], time.time()
     # synthetic episodes are generated on the host (numpy): a few steps ahead, in worker threads, so that the GPU
     # step (~32 ms at batch 8) is not waiting for the generator (~70 ms)
@@ -110,6 +127,8 @@ def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, 
             bucket.allreduce(average=False)     # the sum: FusedAdam applies 1/world inside the update
         else:
             bucket.allreduce()
+            if clip_grad_norm is not None:
+                gnorm = torch.nn.utils.clip_grad_norm_(params, clip_grad_norm)
         opt.step()
         history.append(loss.detach())       # no host sync per step
         if (it + 1) % steps_per_epoch == 0:
@@ -119,7 +138,13 @@ def train(config, steps, batch, size, dev, lr=None, log_every=10, out_dir=None, 
                 os.makedirs(out_dir, exist_ok=True)
                 torch.save({"epoch": epoch, "state_dict": net.state_dict()}, os.path.join(out_dir, f"{epoch:03d}.ckpt"))
         if rank == 0 and log_every and (it + 1) % log_every == 0:
-            print(f"step {it + 1:5d}  loss {float(history[-1]):.4f}  ({(time.time() - t0) / (it + 1) * 1e3:.0f} ms/step)", flush=True)
+            guard = ""
+            if optimizer == "fused" and guarded:
+                gs = opt.guard_stats()
+                guard = f"  gnorm {gs['norm']:.4g}  skipped {gs['skipped']}"
+            elif gnorm is not None:
+                guard = f"  gnorm {float(gnorm):.4g}  skipped 0"
+            print(f"step {it + 1:5d}  loss {float(history[-1]):.4f}{guard}  ({(time.time() - t0) / (it + 1) * 1e3:.0f} ms/step)", flush=True)
     pool.shutdown(wait=False)
     history = [float(v) for v in history]
     if caller_stream is not None:        # hand the thread back on the stream it came with
@@ -141,10 +166,21 @@ def main():
     ap.add_argument("--set_name", default=None, help=".csv / .npy list of the training pids (with --data_dir)")
     ap.add_argument("--optimizer", choices=("torch", "fused"), default="torch", help="torch: torch.optim.Adam (default); fused: "
                     "rpnet_amd.optim.FusedAdam, the Adam update as one HIP launch over the flat gradient bucket")
+    ap.add_argument("--clip_grad_norm", type=float, default=None, help="clip the gradient's 2-norm to this value (yaml key "
+                    "clip_grad_norm; absent: off).  fused: inside the step, on the device; torch: torch.nn.utils.clip_grad_norm_")
+    ap.add_argument("--skip_nonfinite", action="store_true", help="do not take a step whose gradient holds an inf or a NaN (yaml "
+                    "key skip_nonfinite; absent: off).  Needs --optimizer fused")
     a = ap.parse_args()
     if (a.data_dir is None) != (a.set_name is None):
         ap.error("--data_dir and --set_name come together")
     config, _ = load_yaml(a.yaml)
+    clip_grad_norm = a.clip_grad_norm if a.clip_grad_norm is not None else config.get("clip_grad_norm")
+    skip_nonfinite = a.skip_nonfinite or bool(config.get("skip_nonfinite", False))
+    if skip_nonfinite and a.optimizer == "torch":
+        ap.error("--skip_nonfinite needs --optimizer fused: under torch.optim.Adam the decision would take a host read of the "
+                 "gradient norm at every step")
+    if clip_grad_norm is not None and not clip_grad_norm > 0:
+        ap.error(f"--clip_grad_norm {clip_grad_norm}: a threshold above 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     n_dev = torch.cuda.device_count()
     if n_dev == 0:
@@ -170,7 +206,7 @@ def main():
         from rpnet_amd.episodes import DeviceEpisodeSource
         source = DeviceEpisodeSource(a.data_dir, a.set_name, config, dev, rank=int(os.environ.get("RANK", "0")), world=world)
     train(config, a.steps, a.batch or config["batch_size"], a.size, dev, lr=a.lr, out_dir=a.out_dir or config.get("out_dir"),
-          source=source, optimizer=a.optimizer)
+          source=source, optimizer=a.optimizer, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
     if world > 1:
         dist.destroy_process_group()
 
