@@ -22,6 +22,7 @@ import torch
 from . import augment as A
 from . import hip
 from . import registration as R
+from . import surface as SF
 from .hip import call, ptr
 from .utils.volume_reader import FewshotVolumeReader
 from .volume import VolumeSegmenter, dice_from_counts
@@ -162,25 +163,32 @@ class DeviceEvalSource:
                 "supp_pids": [(c, s)], "registration_field": field}
 
 
-def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None):
+def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
     one fp64 table [n_items, 2]; both are copied to the host once, after the last item.  save_pred: a directory that receives every
     volume's mask as <pid>_<class>.nrrd (the masks stay on the device until the tables have crossed).  out: a dict that receives the
-    host tables as out["counts"] and out["ncc"]."""
+    host tables as out["counts"] and out["ncc"].  surface=True: two more device tables, int64 [n_items, 2, K-1, 6] and fp64
+    [n_items, 2, K-1, 2], receive every volume's surface rows (rpnet_amd.surface: the final mask and the affine baseline against the
+    labels) and cross with the others; every item line then ends with ` hd95 <fewshot> (<affine>) assd <fewshot> (<affine>)` (voxels,
+    None where a border is empty), every class line with the means over the items where the figure is not None, and `out` receives
+    out["surface_i"] and out["surface_f"].  The three returned dictionaries are the same either way."""
     from .utils import nrrd
-    seg = VolumeSegmenter(net, batch=batch, graphed=graphed)
+    seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface)
     classes = config["eval_classes"]
     n = len(source) if n_items is None else min(n_items, len(source))
     dev = next(net.parameters()).device
     T, K = net.num_iter, 2
     table = torch.zeros((n, T + 2, K - 1, 3), device=dev, dtype=torch.int64)
     ncc = torch.zeros((n, 2), device=dev, dtype=torch.float64)
+    surf_i = torch.zeros((n, 2, K - 1, SF.IROW), device=dev, dtype=torch.int64) if surface else None
+    surf_f = torch.zeros((n, 2, K - 1, SF.FROW), device=dev, dtype=torch.float64) if surface else None
     meta, masks = [], []
     for j in range(n):
         s = source.item(j)
-        res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j])
+        res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j],
+                  **({"surface_out": (surf_i[j], surf_f[j])} if surface else {}))
         ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
         meta.append((s["pid"], classes[s["class_id"]]))
         if save_pred:
@@ -188,6 +196,11 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     counts, ncc = table.cpu().numpy(), ncc.cpu().numpy()          # the two transfers of the data set
     if out is not None:
         out["counts"], out["ncc"] = counts, ncc
+    surf_few, surf_aff = defaultdict(list), defaultdict(list)
+    if surface:
+        surf_i, surf_f = surf_i.cpu().numpy(), surf_f.cpu().numpy()
+        if out is not None:
+            out["surface_i"], out["surface_f"] = surf_i, surf_f
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
     if save_pred:
         os.makedirs(save_pred, exist_ok=True)
@@ -200,10 +213,16 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             d = dice_from_counts(counts[j, k])[0]
             dsc_ref[name][k].append(d)
             line += f" ref {k} {d},"
+        if surface:
+            few, aff = SF.surface_figures(surf_i[j, :, 0], surf_f[j, :, 0])
+            surf_few[name].append(few)
+            surf_aff[name].append(aff)
+            line += SF.line_suffix(few, aff)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
     for name in classes:
         if dsc_fewshot[name]:
-            print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}")
+            print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
+                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else ""))
     return dsc_affine, dsc_fewshot, dsc_ref

@@ -168,6 +168,16 @@ _GUARD_SIGS = {
 GUARD_ABI_SYMBOLS = tuple(_GUARD_SIGS)
 GUARD_ABI_VERSION = 1     # RPNET_GUARD_ABI_VERSION of include/rpnet_guard_abi.h
 
+# the surface-distance tallies of an evaluated volume: include/rpnet_surface_abi.h (additions beside the four headers above; their
+# ledger is tests/surface_abi_ledger.py)
+_SURFACE_SIGS = {
+    "rpnet_surface_abi_version": (ci, []),
+    "rpnet_surface_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_surface_tally": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+SURFACE_ABI_SYMBOLS = tuple(_SURFACE_SIGS)
+SURFACE_ABI_VERSION = 1     # RPNET_SURFACE_ABI_VERSION of include/rpnet_surface_abi.h
+
 
 def lib_path():
     return _LIB_PATH
@@ -185,7 +195,8 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        for name, (res, args) in list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()) + list(_GUARD_SIGS.items()):
+        for name, (res, args) in (list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()) + list(_GUARD_SIGS.items())
+                                  + list(_SURFACE_SIGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
@@ -199,6 +210,9 @@ def load():
         if lib.rpnet_guard_abi_version() != GUARD_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has gradient-guard ABI version {lib.rpnet_guard_abi_version()}, this binding was written for "
                                f"{GUARD_ABI_VERSION} (include/rpnet_guard_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
+        if lib.rpnet_surface_abi_version() != SURFACE_ABI_VERSION:
+            raise RuntimeError(f"{_LIB_PATH} has surface-distance ABI version {lib.rpnet_surface_abi_version()}, this binding was written "
+                               f"for {SURFACE_ABI_VERSION} (include/rpnet_surface_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

@@ -15,9 +15,14 @@ from collections import namedtuple
 import torch
 
 from . import hip
+from . import surface as SF
 from .graph import GraphedEval
 
-VolumeResult = namedtuple("VolumeResult", ["mask", "counts", "dice"])
+
+class VolumeResult(namedtuple("VolumeResult", ["mask", "counts", "dice"])):
+    """(mask, counts, dice) of a volume; `surface` beside them: None, or the surface distances of VolumeSegmenter(surface=True)"""
+    surface = None
+
 
 # One GraphedEval per net, shared by every VolumeSegmenter of that net.  A captured graph holds the addresses of the net's weight
 # packs, and a second `GraphedEval(net)` clears that cache (graph.py:__init__): the first wrapper's graphs would then replay on
@@ -67,6 +72,19 @@ def seg_tally(sources, kinds, n_valid, labels=None, counts=None, mask=None, mask
              mask_src, N, K, H, W)
 
 
+def check_surface_out(surface_out, K):
+    """the tables of surface rows a caller hands to VolumeSegmenter: (int64 [2, K-1, 6], float64 [2, K-1, 2]), both contiguous: rows of
+    the final mask, then of the affine baseline, per foreground class"""
+    ok = isinstance(surface_out, (tuple, list)) and len(surface_out) == 2 and all(torch.is_tensor(t) and t.is_contiguous() for t in surface_out)
+    if ok:
+        it, ft = surface_out
+        ok = (it.dtype == torch.int64 and tuple(it.shape) == (2, K - 1, SF.IROW) and ft.dtype == torch.float64
+              and tuple(ft.shape) == (2, K - 1, SF.FROW))
+    if not ok:
+        raise ValueError(f"surface_out must be a pair of contiguous tensors (int64 [2, {K - 1}, {SF.IROW}], float64 [2, {K - 1}, {SF.FROW}]): "
+                         "the rows of the final mask and of the affine baseline per foreground class")
+
+
 def check_counts_out(counts_out, K, T=None):
     """the tally table a caller hands to VolumeSegmenter: a contiguous int64 tensor [T+2, K-1, 3] (T is checked where it is known)"""
     if not torch.is_tensor(counts_out) or counts_out.dtype != torch.int64 or not counts_out.is_contiguous():
@@ -78,8 +96,8 @@ def check_counts_out(counts_out, K, T=None):
 
 
 class VolumeSegmenter:
-    """`VolumeSegmenter(net, batch=8, graphed=True)(support_images, support_fg, query_images, appr_query_labels, query_labels=None,
-    counts_out=None)` -> VolumeResult(mask, counts, dice).
+    """`VolumeSegmenter(net, batch=8, graphed=True, surface=False)(support_images, support_fg, query_images, appr_query_labels,
+    query_labels=None, counts_out=None, surface_out=None)` -> VolumeResult(mask, counts, dice).
 
     Arguments are the volume-level tensors of a `FewshotRegReader` eval item: nested lists `[way][shot]` of support images
     [S,1,H,W] and foreground masks [S,H,W] (background = 1 - foreground), query images [S,1,H,W], the approximate (affine) labels
@@ -95,12 +113,19 @@ class VolumeSegmenter:
     only device-to-host transfer this class adds is the counter table, once per volume.
       counts_out  an int64 tensor [T+2, K-1, 3] on the net's device (needs query_labels): the tallies are ADDED to it, nothing crosses
                   to the host, and `counts` and `dice` of the result are None — for a caller that keeps the tables of many volumes
-                  on the device and fetches them once (rpnet_amd.dataset_eval.evaluate_dataset)."""
+                  on the device and fetches them once (rpnet_amd.dataset_eval.evaluate_dataset).
+      surface=True  (needs query_labels to do anything) the completed volume gets two surface tallies per foreground class
+                  (rpnet_amd.surface.surface_tally): the final mask against the labels and appr_query_labels against the labels.  The
+                  result's `surface` is {'fewshot': [..], 'affine': [..]}, per class a dict {'hd95', 'hd', 'assd'} in voxels (None
+                  where a border is empty); the two small tables cross to the host once per volume.  Nothing else changes: mask,
+                  counts and dice are those of surface=False.
+      surface_out (int64 [2, K-1, 6], float64 [2, K-1, 2]) on the net's device (needs surface=True and query_labels): the rows are
+                  written there, nothing crosses to the host for them and the result's `surface` is None."""
 
-    def __init__(self, net, batch=8, graphed=True):
+    def __init__(self, net, batch=8, graphed=True, surface=False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
-        self.net, self.batch, self.graphed = net.eval(), int(batch), bool(graphed)
+        self.net, self.batch, self.graphed, self.surface = net.eval(), int(batch), bool(graphed), bool(surface)
         self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
         if self._graphed_eval is not None and self._graphed_eval.net is not net:
             raise ValueError("VolumeSegmenter: the GraphedEval handed in wraps another net")
@@ -134,7 +159,24 @@ class VolumeSegmenter:
         tab[0][len(tab[2])] = appr.data_ptr()
         return tab
 
-    def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None):
+    def _surface(self, mask, appr, labels, K, surface_out):
+        """the rows of the final mask (0) and the affine baseline (1) against the labels, per foreground class"""
+        dev = mask.device
+        if surface_out is not None:
+            itab, ftab = surface_out
+        else:
+            itab = torch.zeros((2, K - 1, SF.IROW), device=dev, dtype=torch.int64)
+            ftab = torch.zeros((2, K - 1, SF.FROW), device=dev, dtype=torch.float64)
+        it, ft = itab.view(-1, SF.IROW), ftab.view(-1, SF.FROW)
+        for s, pred in enumerate((mask, appr)):
+            for c in range(1, K):
+                SF.surface_tally(pred, labels, it, s * (K - 1) + c - 1, ft, s * (K - 1) + c - 1, cls=c)
+        if surface_out is not None:
+            return None
+        figures = SF.surface_figures(itab.cpu().numpy(), ftab.cpu().numpy())
+        return {"fewshot": figures[:K - 1], "affine": figures[K - 1:]}
+
+    def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None):
         dev = next(self.net.parameters()).device
         n_ways, n_shots = len(support_images), len(support_images[0])
         S, B = query_images.shape[0], self.batch
@@ -146,6 +188,14 @@ class VolumeSegmenter:
             check_counts_out(counts_out, K, getattr(self.net, "num_iter", None))
             if counts_out.device != dev:
                 raise ValueError(f"counts_out is on {counts_out.device}, the net on {dev}")
+        if surface_out is not None:
+            if not self.surface:
+                raise ValueError("surface_out needs VolumeSegmenter(surface=True)")
+            if query_labels is None:
+                raise ValueError("surface_out needs query_labels (a surface distance is measured against the ground truth)")
+            check_surface_out(surface_out, K)
+            if any(t.device != dev for t in surface_out):
+                raise ValueError(f"surface_out is on {surface_out[0].device}, the net on {dev}")
         nb = -(-S // B)
         pad = nb * B - S
 
@@ -184,10 +234,15 @@ class VolumeSegmenter:
                     nv_now = n_valid
                 seg_tally(tab[2] + [appr[sl]], [0] * (T + 1) + [1], self._nv, labels[sl] if labels is not None else None, counts,
                           mask[sl], mask_src=T, K=K, _table=tab)
+            surface = self._surface(mask[:S], appr[:S], labels[:S], K, surface_out) if self.surface and labels is not None else None
         if counts is None or counts_out is not None:
-            return VolumeResult(mask[:S], None, None)
-        host = counts.cpu().numpy()                 # the one transfer of the volume
-        T = host.shape[0] - 2
-        dice = {"fewshot": dice_from_counts(host[T]), "affine": dice_from_counts(host[T + 1]),
-                "refinement": {i: dice_from_counts(host[i]) for i in range(T)}}
-        return VolumeResult(mask[:S], host, dice)
+            res = VolumeResult(mask[:S], None, None)
+        else:
+            host = counts.cpu().numpy()                 # the one transfer of the volume
+            T = host.shape[0] - 2
+            dice = {"fewshot": dice_from_counts(host[T]), "affine": dice_from_counts(host[T + 1]),
+                    "refinement": {i: dice_from_counts(host[i]) for i in range(T)}}
+            res = VolumeResult(mask[:S], host, dice)
+        if surface is not None:
+            res.surface = surface
+        return res

@@ -5,13 +5,17 @@ iteration), using only the symbols that driver imports, at the reference's impor
 The reference file itself cannot run offline (it needs tensorboard and the private data).
 
     python tools/eval_driver.py --yaml yamls/example.yml [--items 2] [--on-device] [--device-items] [--batch 8] [--save-pred DIR]
+                                [--surface]
 
 --on-device: the same lines from rpnet_amd.volume.VolumeSegmenter (masks and Dice tallies on the device, one transfer per volume,
 `--batch` slices per model call through the captured graph); --save-pred DIR writes each volume's predicted mask as
 DIR/<pid>_<class>.nrrd (uint8, gzip) and implies --on-device.  --device-items (implies --on-device; needs NRRD volumes under the
 yaml's data_dir): the items too are built on the device (rpnet_amd.dataset_eval.DeviceEvalSource: volumes cached in HBM, one gather
 launch and the registration launches per item) and the tallies and both image similarity figures of all volumes cross to the host
-once, after the last volume (rpnet_amd.dataset_eval.evaluate_dataset).
+once, after the last volume (rpnet_amd.dataset_eval.evaluate_dataset).  --surface (implies --on-device; works with --device-items):
+every item line ends with ` hd95 <fewshot> (<affine>) assd <fewshot> (<affine>)`, the 95th-percentile Hausdorff and the average
+symmetric surface distance of the final mask and of the affine baseline in voxels (rpnet_amd.surface), every class line with their
+means.
 """
 import argparse
 import os
@@ -68,13 +72,18 @@ def evaluate(net, loader, config, n_items=None, batch_size=2):
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
-def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None):
+def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None, surface=False):
     """`evaluate` through rpnet_amd.volume.VolumeSegmenter: the same printed lines and return value; thresholds, Dice tallies and the
     predicted mask are formed on the device, the tallies cross to the host once per volume.  save_pred: a directory that receives
-    every volume's mask as <pid>_<class>.nrrd; segmenter: a VolumeSegmenter to reuse (its captured graphs live with it)."""
+    every volume's mask as <pid>_<class>.nrrd; segmenter: a VolumeSegmenter to reuse (its captured graphs live with it); surface: the
+    lines gain the surface distances of rpnet_amd.surface (a segmenter handed in must have been made with surface=True)."""
+    from rpnet_amd import surface as SF
     from rpnet_amd.utils import nrrd
     from rpnet_amd.volume import VolumeSegmenter
-    seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed)
+    seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed, surface=surface)
+    if surface and not seg.surface:
+        raise ValueError("evaluate_on_device(surface=True) needs a VolumeSegmenter(surface=True)")
+    surf_few, surf_aff = defaultdict(list), defaultdict(list)
     classes = config["eval_classes"]
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
     if save_pred:
@@ -92,12 +101,18 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
         for k, d in res.dice["refinement"].items():
             dsc_ref[name][k].append(d[0])
             line += f" ref {k} {d[0]},"
+        if surface:
+            few, aff = res.surface["fewshot"][0], res.surface["affine"][0]
+            surf_few[name].append(few)
+            surf_aff[name].append(aff)
+            line += SF.line_suffix(few, aff)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), res.mask.cpu().numpy(), encoding="gzip")
     for name in classes:
         if dsc_fewshot[name]:
-            print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}")
+            print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
+                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else ""))
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
@@ -110,6 +125,8 @@ def main():
     ap.add_argument("--save-pred", default=None, metavar="DIR", help="write each volume's mask as DIR/<pid>_<class>.nrrd; implies --on-device")
     ap.add_argument("--device-items", action="store_true",
                     help="build the items on the device too and fetch all tallies once (rpnet_amd.dataset_eval); implies --on-device")
+    ap.add_argument("--surface", action="store_true",
+                    help="HD95 and ASSD of the final mask and the affine baseline at the end of every line (rpnet_amd.surface); implies --on-device")
     a = ap.parse_args()
     config, args = load_yaml(a.yaml)
     config["n_iter_refinement"] = config["n_test_iter_refinement"]            # test_rpnet.py:51
@@ -124,9 +141,9 @@ def main():
         from rpnet_amd.dataset_eval import DeviceEvalSource, evaluate_dataset
         source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device)
         source.warm()
-        evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred)
-    elif a.on_device or a.save_pred:
-        evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred)
+        evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface)
+    elif a.on_device or a.save_pred or a.surface:
+        evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred, surface=a.surface)
     else:
         evaluate(net, loader, config, a.items, a.batch or 2)
 
