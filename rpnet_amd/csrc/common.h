@@ -46,6 +46,11 @@ __device__ __forceinline__ double block_sum256(double v, double* smem4) {
     return smem4[0] + smem4[1] + smem4[2] + smem4[3];
 }
 
+// Cell index of a bilinear sampling position's floor, for an axis of n pixels.  A position far outside the image (|coordinate|
+// beyond the int range, or NaN) is outside either way, and converting it to int unclamped is undefined: clamp first.  Every
+// value the clamp changes lies outside [-1, n - 1], where both corners of the cell read as zero padding.
+__device__ __forceinline__ int sample_cell(float floored, int n) { return (int)fminf(fmaxf(floored, -2.f), (float)n + 1.f); }
+
 // First statement of every HBM-bound pass of the main chain.  A SIMD issues vector instructions of all resident waves through one
 // port: beside a resident GEMM wave — the default schedule runs the weight gradients of a layer on a side stream beside the passes
 // of the layer below — a pass instruction waits for a gap in that wave's MFMA stream, and the pass takes 2.7 x (BatchNorm backward)

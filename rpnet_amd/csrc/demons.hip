@@ -31,8 +31,7 @@ __device__ __forceinline__ Corners corners(float lx, float ly, int H, int W) {
     const float fx = floorf(ix), fy = floorf(iy);
     Corners c;
     c.w = ix - fx; c.e = 1.f - c.w; c.n = iy - fy; c.s = 1.f - c.n;
-    // positions far outside (|coordinate| beyond int range) are outside either way: clamp before the conversion
-    const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
+    const int x0 = sample_cell(fx, W), y0 = sample_cell(fy, H);
     const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
     const bool yin0 = y0 >= 0 && y0 < H, yin1 = y0 + 1 >= 0 && y0 + 1 < H;
     c.idx[0] = (xin0 && yin0) ? y0 * W + x0 : -1;

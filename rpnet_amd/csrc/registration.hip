@@ -26,7 +26,7 @@ struct Bilinear {
 
 __device__ __forceinline__ Bilinear sample_zeros(const float* __restrict__ img, int H, int W, float ix, float iy) {
     const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
+    const int x0 = sample_cell(fx, W), y0 = sample_cell(fy, H);
     const float tx = ix - fx, ty = iy - fy;
     const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
     const bool yin0 = y0 >= 0 && y0 < H, yin1 = y0 + 1 >= 0 && y0 + 1 < H;

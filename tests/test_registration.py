@@ -164,7 +164,8 @@ def test_hip_demons_stage_vs_oracle(golden, tag):
     order); after 50 steps within 5e-3 of a field of magnitude 0.03 (measured 9e-8 ... 6e-5 in most runs, above 1e-3 in
     about one run in ten: the order of the fp32 atomics changes and the optimisation amplifies rounding — one different
     ulp moved the CPU oracle's own flow by 9e-4 — as it does between two runs of the reference's own CUDA backward);
-    NCC at the last evaluated flow within 1e-3; displacement and warp against the oracle's on the HIP flow."""
+    NCC at the last evaluated flow within 1e-3; displacement and warp against the oracle's on the HIP flow.
+    The tight check of a single gradient (float64, linearised Adam step) lives in tests/test_gpu_registration_fp64.py."""
     from oracle import registration_oracle as RO
     from rpnet_amd import registration as R
     g = golden("registration_demons")
