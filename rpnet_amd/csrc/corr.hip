@@ -235,7 +235,7 @@ int launch_corr_transpose(const float* dcorr, float* dct, int B, int h, int w, i
 
 }  // namespace rpnet
 
-#define RPNET_CORR_DISPATCH(R_, ...)                         \
+#define RPNET_CORR_DISPATCH(NAME_, R_, ...)                  \
     switch (R_) {                                              \
         case 1: { constexpr int RR = 1; __VA_ARGS__; } break;         \
         case 2: { constexpr int RR = 2; __VA_ARGS__; } break;         \
@@ -244,7 +244,7 @@ int launch_corr_transpose(const float* dcorr, float* dct, int B, int h, int w, i
         case 5: { constexpr int RR = 5; __VA_ARGS__; } break;         \
         case 6: { constexpr int RR = 6; __VA_ARGS__; } break;         \
         case 7: { constexpr int RR = 7; __VA_ARGS__; } break;         \
-        default: rpnet::set_error("local_corr: radius %d not in 1..7", R_); return RPNET_ERR_SHAPE; \
+        default: rpnet::set_error(NAME_ ": radius %d not in 1..7", R_); return RPNET_ERR_SHAPE; \
     }
 
 extern "C" int rpnet_local_corr_fwd(const float* f1, const float* f2, float* corr, int B, int h, int w, int C, int r,
@@ -254,7 +254,7 @@ extern "C" int rpnet_local_corr_fwd(const float* f1, const float* f2, float* cor
     RPNET_REQUIRE(C % CC == 0 && cstride >= (2 * r + 1) * (2 * r + 1) && cstride <= 256, RPNET_ERR_SHAPE,
                   "local_corr_fwd: C=%d (multiple of 32) cstride=%d", C, cstride);
     int rc = 0;
-    RPNET_CORR_DISPATCH(r, rc = corr_fwd_launch<RR>(f1, f2, corr, B, h, w, C, cstride, (hipStream_t)stream));
+    RPNET_CORR_DISPATCH("local_corr_fwd", r, rc = corr_fwd_launch<RR>(f1, f2, corr, B, h, w, C, cstride, (hipStream_t)stream));
     return rc;
 }
 
@@ -278,7 +278,7 @@ extern "C" int rpnet_local_corr_bwd(const float* f1, const float* f2, const floa
     const size_t total = (size_t)B * h * w * cstride;
     int nb = (int)((total + 255) / 256);
     if (nb > 16384) nb = 16384;
-    RPNET_CORR_DISPATCH(r, {
+    RPNET_CORR_DISPATCH("local_corr_bwd", r, {
         constexpr int K = 2 * RR + 1, HT = CT + 2 * RR, KA = (K + 3) & ~3;
         constexpr int BCT = RR <= 5 ? 64 : 32;
         const size_t lds = (size_t)(HT * HT * (BCT + 4) + 64 * K * KA) * sizeof(float);

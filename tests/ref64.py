@@ -6,6 +6,8 @@ nothing is built from oracle/rpnet_oracle.py (tests/test_host_ref64.py compares 
 Layouts are the kernels' own: feature maps NHWC ([B, h, w, C] or [B, hw, C]), logits / predictions NCHW, masks
 [nmask, B, H, W].  Every function takes `dtype`: float64 is the reference, float32 the yardstick — the same operators at the
 kernels' precision, whose distance from the float64 result says what fp32 round-off costs on these inputs."""
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -227,3 +229,28 @@ def rowdot_scale(g, x, s, mode, dtype=F64):
 def bn_act_bound(gamma, beta, n, dtype=F64):
     """max_c |gamma_c| sqrt(n) + |beta_c|: |xhat| <= sqrt(n) for any batch of n values per channel"""
     return (_c(gamma, dtype).abs() * float(n) ** 0.5 + _c(beta, dtype).abs()).max()
+
+
+# ------------------------------------------------- local-window correlation (Correlation(), net/rp_net.py:153-181), NHWC
+def _local_corr(f1, f2, r, cstride=None):
+    # f2 padded by r with zeros, one shifted product per offset: a (horizontal) is the major index of the window channel
+    B, h, w, C = f1.shape
+    K = 2 * r + 1
+    f2p = F.pad(f2, (0, 0, r, r, r, r))
+    cols = [(f1 * f2p[:, c:c + h, a:a + w]).sum(-1) for a in range(K) for c in range(K)]
+    out = torch.stack(cols, -1) / math.sqrt(C)
+    return out if cstride is None or cstride == K * K else F.pad(out, (0, cstride - K * K))
+
+
+def local_corr(f1, f2, r, cstride=None, dtype=F64):
+    """f1, f2 [B, h, w, C] -> corr [B, h, w, cstride or KK]:
+    corr[b,y,x, a*K + c] = <f1[b,y,x,:], f2[b, y+c-r, x+a-r, :]> / sqrt(C), zero outside the image and in the pad channels"""
+    return _local_corr(_c(f1, dtype), _c(f2, dtype), r, cstride)
+
+
+def local_corr_bwd(f1, f2, dcorr, r, df1_add=None, dtype=F64):
+    """dcorr [B, h, w, >= KK] (channels at or beyond KK are ignored) -> (df1 (+ df1_add), df2)"""
+    f1, f2 = _c(f1, dtype).requires_grad_(True), _c(f2, dtype).requires_grad_(True)
+    KK = (2 * r + 1) ** 2
+    g1, g2 = torch.autograd.grad(_local_corr(f1, f2, r), (f1, f2), _c(dcorr, dtype)[..., :KK])
+    return (g1 if df1_add is None else g1 + _c(df1_add, dtype)), g2

@@ -66,3 +66,50 @@ def test_float32_is_the_same_code():
     f, p = rnd(9, 2, 30, 16), rnd(10, 2, 3, 16)
     a, b = R.cosine_match(f, p), R.cosine_match(f, p, dtype=torch.float32)
     assert a.dtype == torch.float64 and b.dtype == torch.float32 and 0 < rel_err(b, a) < 1e-5
+
+
+def nhwc(x):
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
+@pytest.mark.parametrize("B,C,h,w,r", [(2, 8, 7, 9, 3), (1, 64, 3, 5, 5)])
+def test_local_corr_is_the_oracles(B, C, h, w, r):
+    from oracle import rpnet_oracle as O
+    f1, f2, go = rnd(21, B, h, w, C), rnd(22, B, h, w, C), rnd(23, B, h, w, (2 * r + 1) ** 2 + 3)
+    a, b = nchw(f1, h, w).double().requires_grad_(True), nchw(f2, h, w).double().requires_grad_(True)
+    ref = O.local_correlation(a, b, r)
+    kk = ref.shape[1]
+    g1, g2 = torch.autograd.grad(ref, (a, b), go[..., :kk].permute(0, 3, 1, 2).double())
+    out = R.local_corr(f1, f2, r, cstride=kk + 3)
+    assert out.dtype == torch.float64 and out.shape == (B, h, w, kk + 3) and out[..., kk:].abs().max() == 0
+    assert rel_err(out[..., :kk], nhwc(ref)) < 1e-12
+    add = rnd(24, B, h, w, C)
+    d1, d2 = R.local_corr_bwd(f1, f2, go, r, df1_add=add)         # the three channels of go beyond KK are ignored
+    assert rel_err(d1, nhwc(g1) + add.double()) < 1e-12 and rel_err(d2, nhwc(g2)) < 1e-12
+    assert torch.equal(R.local_corr_bwd(f1, f2, go, r)[1], d2)
+
+
+def test_local_corr_is_the_recorded_correlation():
+    """corr_r5_* of tests/golden/ops.npz: the reference's own Correlation() and its autograd in float32 (the inputs are those of
+    tests/test_gpu_ops.py::test_local_correlation_golden)"""
+    import os
+    import numpy as np
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ops.npz"))
+    b, c, h, w, r = (int(v) for v in g["corr_r5_dims"])
+    f1, f2, go = nhwc(rnd(11, b, c, h, w)), nhwc(rnd(12, b, c, h, w)), nhwc(rnd(13, b, 121, h, w))
+    assert rel_err(R.local_corr(f1, f2, r), nhwc(torch.from_numpy(g["corr_r5_out"]))) < 1e-5
+    d1, d2 = R.local_corr_bwd(f1, f2, go, r)
+    assert rel_err(d1, nhwc(torch.from_numpy(g["corr_r5_g1"]))) < 1e-5 and rel_err(d2, nhwc(torch.from_numpy(g["corr_r5_g2"]))) < 1e-5
+
+
+def test_local_corr_outside_the_image_is_exactly_zero():
+    B, h, w, C, r = 2, 3, 5, 8, 5
+    K = 2 * r + 1
+    out = R.local_corr(rnd(25, B, h, w, C) + 3, rnd(26, B, h, w, C) + 3, r).reshape(B, h, w, K, K)      # [.., a, c]
+    for y in range(h):
+        for x in range(w):
+            for a in range(K):
+                for c in range(K):
+                    inside = 0 <= y + c - r < h and 0 <= x + a - r < w
+                    assert inside or (out[:, y, x, a, c] == 0.0).all()
+                    assert not inside or (out[:, y, x, a, c] != 0.0).all()
