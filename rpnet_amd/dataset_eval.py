@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import augment as A
+from . import components as CC
 from . import hip
 from . import registration as R
 from . import surface as SF
@@ -163,7 +164,7 @@ class DeviceEvalSource:
                 "supp_pids": [(c, s)], "registration_field": field}
 
 
-def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False):
+def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -173,9 +174,16 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     [n_items, 2, K-1, 2], receive every volume's surface rows (rpnet_amd.surface: the final mask and the affine baseline against the
     labels) and cross with the others; every item line then ends with ` hd95 <fewshot> (<affine>) assd <fewshot> (<affine>)` (voxels,
     None where a border is empty), every class line with the means over the items where the figure is not None, and `out` receives
-    out["surface_i"] and out["surface_f"].  The three returned dictionaries are the same either way."""
+    out["surface_i"] and out["surface_f"].  keep_largest (False, True = 6, 6 or 26): every volume's final mask is also filtered to the
+    largest connected component of its class (rpnet_amd.components); two more device tables, int64 [n_items, K-1, 3] (Dice counts of the
+    filtered mask) and int64 [n_items, K-1, 4] (component statistics), and with surface=True an int64 [n_items, K-1, 6] and an fp64
+    [n_items, K-1, 2] table (its surface rows), cross with the others; every item line then ends with
+    ` lcc <dice> (<n_components> components, <removed> voxels removed)`, followed by ` lcc hd95 <v> assd <v>` under surface, every class
+    line with their means; `out` receives out["post_counts"], out["components"] and, with surface, out["post_surface_i"] and
+    out["post_surface_f"]; save_pred writes the filtered mask.  The three returned dictionaries are the same either way."""
     from .utils import nrrd
-    seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface)
+    conn = CC.connectivity_of(keep_largest)
+    seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False)
     classes = config["eval_classes"]
     n = len(source) if n_items is None else min(n_items, len(source))
     dev = next(net.parameters()).device
@@ -184,15 +192,22 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     ncc = torch.zeros((n, 2), device=dev, dtype=torch.float64)
     surf_i = torch.zeros((n, 2, K - 1, SF.IROW), device=dev, dtype=torch.int64) if surface else None
     surf_f = torch.zeros((n, 2, K - 1, SF.FROW), device=dev, dtype=torch.float64) if surface else None
+    post_c = torch.zeros((n, K - 1, CC.COUNTS_ROW), device=dev, dtype=torch.int64) if conn else None
+    post_s = torch.zeros((n, K - 1, CC.STATS_ROW), device=dev, dtype=torch.int64) if conn else None
+    post_i = torch.zeros((n, K - 1, SF.IROW), device=dev, dtype=torch.int64) if conn and surface else None
+    post_f = torch.zeros((n, K - 1, SF.FROW), device=dev, dtype=torch.float64) if conn and surface else None
     meta, masks = [], []
     for j in range(n):
         s = source.item(j)
+        extra = {"surface_out": (surf_i[j], surf_f[j])} if surface else {}
+        if conn:
+            extra["post_out"] = (post_c[j], post_s[j]) + (((post_i[j], post_f[j]),) if surface else ())
         res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j],
-                  **({"surface_out": (surf_i[j], surf_f[j])} if surface else {}))
+                  **extra)
         ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
         meta.append((s["pid"], classes[s["class_id"]]))
         if save_pred:
-            masks.append(res.mask)
+            masks.append(res.post["mask"] if conn else res.mask)
     counts, ncc = table.cpu().numpy(), ncc.cpu().numpy()          # the two transfers of the data set
     if out is not None:
         out["counts"], out["ncc"] = counts, ncc
@@ -201,6 +216,15 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
         surf_i, surf_f = surf_i.cpu().numpy(), surf_f.cpu().numpy()
         if out is not None:
             out["surface_i"], out["surface_f"] = surf_i, surf_f
+    lcc_dice, lcc_fig, lcc_surf = defaultdict(list), defaultdict(list), defaultdict(list)
+    if conn:
+        post_c, post_s = post_c.cpu().numpy(), post_s.cpu().numpy()
+        if out is not None:
+            out["post_counts"], out["components"] = post_c, post_s
+        if surface:
+            post_i, post_f = post_i.cpu().numpy(), post_f.cpu().numpy()
+            if out is not None:
+                out["post_surface_i"], out["post_surface_f"] = post_i, post_f
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
     if save_pred:
         os.makedirs(save_pred, exist_ok=True)
@@ -218,11 +242,19 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             surf_few[name].append(few)
             surf_aff[name].append(aff)
             line += SF.line_suffix(few, aff)
+        if conn:
+            d_lcc, fig = dice_from_counts(post_c[j])[0], CC.components_figures(post_s[j])[0]
+            kept = SF.surface_figures(post_i[j], post_f[j])[0] if surface else None
+            lcc_dice[name].append(d_lcc)
+            lcc_fig[name].append(fig)
+            lcc_surf[name].append(kept)
+            line += CC.line_suffix(d_lcc, fig, kept)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
     for name in classes:
         if dsc_fewshot[name]:
             print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
-                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else ""))
+                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else "")
+                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None) if conn else ""))
     return dsc_affine, dsc_fewshot, dsc_ref

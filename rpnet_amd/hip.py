@@ -178,6 +178,17 @@ _SURFACE_SIGS = {
 SURFACE_ABI_SYMBOLS = tuple(_SURFACE_SIGS)
 SURFACE_ABI_VERSION = 1     # RPNET_SURFACE_ABI_VERSION of include/rpnet_surface_abi.h
 
+# connected components of an evaluated volume and the largest-component filter: include/rpnet_cc_abi.h (additions beside the five
+# headers above; their ledger is tests/cc_abi_ledger.py)
+_CC_SIGS = {
+    "rpnet_cc_abi_version": (ci, []),
+    "rpnet_cc_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_cc_label": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+    "rpnet_cc_keep_largest": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+CC_ABI_SYMBOLS = tuple(_CC_SIGS)
+CC_ABI_VERSION = 1     # RPNET_CC_ABI_VERSION of include/rpnet_cc_abi.h
+
 
 def lib_path():
     return _LIB_PATH
@@ -196,7 +207,7 @@ def load():
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
         for name, (res, args) in (list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()) + list(_GUARD_SIGS.items())
-                                  + list(_SURFACE_SIGS.items())):
+                                  + list(_SURFACE_SIGS.items()) + list(_CC_SIGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
@@ -213,6 +224,9 @@ def load():
         if lib.rpnet_surface_abi_version() != SURFACE_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has surface-distance ABI version {lib.rpnet_surface_abi_version()}, this binding was written "
                                f"for {SURFACE_ABI_VERSION} (include/rpnet_surface_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
+        if lib.rpnet_cc_abi_version() != CC_ABI_VERSION:
+            raise RuntimeError(f"{_LIB_PATH} has connected-component ABI version {lib.rpnet_cc_abi_version()}, this binding was written "
+                               f"for {CC_ABI_VERSION} (include/rpnet_cc_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

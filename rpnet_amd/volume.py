@@ -14,14 +14,17 @@ from collections import namedtuple
 
 import torch
 
+from . import components as CC
 from . import hip
 from . import surface as SF
 from .graph import GraphedEval
 
 
 class VolumeResult(namedtuple("VolumeResult", ["mask", "counts", "dice"])):
-    """(mask, counts, dice) of a volume; `surface` beside them: None, or the surface distances of VolumeSegmenter(surface=True)"""
+    """(mask, counts, dice) of a volume; `surface` beside them: None, or the surface distances of VolumeSegmenter(surface=True);
+    `post`: None, or what VolumeSegmenter(keep_largest=...) measured on the mask filtered to its largest components"""
     surface = None
+    post = None
 
 
 # One GraphedEval per net, shared by every VolumeSegmenter of that net.  A captured graph holds the addresses of the net's weight
@@ -85,6 +88,27 @@ def check_surface_out(surface_out, K):
                          "the rows of the final mask and of the affine baseline per foreground class")
 
 
+def check_post_out(post_out, K, surface):
+    """the tables a caller hands to VolumeSegmenter(keep_largest=...): (counts int64 [K-1, 3], stats int64 [K-1, 4]) and, with
+    surface=True, a third member (int64 [K-1, 6], float64 [K-1, 2]); all contiguous: one row per foreground class of the filtered mask"""
+    want = 3 if surface else 2
+    ok = isinstance(post_out, (tuple, list)) and len(post_out) == want and all(torch.is_tensor(t) and t.is_contiguous() for t in post_out[:2])
+    if ok:
+        counts, stats = post_out[:2]
+        ok = (counts.dtype == torch.int64 and tuple(counts.shape) == (K - 1, CC.COUNTS_ROW) and stats.dtype == torch.int64
+              and tuple(stats.shape) == (K - 1, CC.STATS_ROW))
+    if ok and surface:
+        pair = post_out[2]
+        ok = isinstance(pair, (tuple, list)) and len(pair) == 2 and all(torch.is_tensor(t) and t.is_contiguous() for t in pair)
+        ok = ok and (pair[0].dtype == torch.int64 and tuple(pair[0].shape) == (K - 1, SF.IROW) and pair[1].dtype == torch.float64
+                     and tuple(pair[1].shape) == (K - 1, SF.FROW))
+    if not ok:
+        raise ValueError(f"post_out must be contiguous tensors (int64 [{K - 1}, {CC.COUNTS_ROW}], int64 [{K - 1}, {CC.STATS_ROW}]"
+                         + (f", (int64 [{K - 1}, {SF.IROW}], float64 [{K - 1}, {SF.FROW}])" if surface else "")
+                         + "): the Dice counts, the component statistics" + (" and the surface rows" if surface else "")
+                         + " of the filtered mask per foreground class")
+
+
 def check_counts_out(counts_out, K, T=None):
     """the tally table a caller hands to VolumeSegmenter: a contiguous int64 tensor [T+2, K-1, 3] (T is checked where it is known)"""
     if not torch.is_tensor(counts_out) or counts_out.dtype != torch.int64 or not counts_out.is_contiguous():
@@ -96,8 +120,8 @@ def check_counts_out(counts_out, K, T=None):
 
 
 class VolumeSegmenter:
-    """`VolumeSegmenter(net, batch=8, graphed=True, surface=False)(support_images, support_fg, query_images, appr_query_labels,
-    query_labels=None, counts_out=None, surface_out=None)` -> VolumeResult(mask, counts, dice).
+    """`VolumeSegmenter(net, batch=8, graphed=True, surface=False, keep_largest=False)(support_images, support_fg, query_images,
+    appr_query_labels, query_labels=None, counts_out=None, surface_out=None, post_out=None)` -> VolumeResult(mask, counts, dice).
 
     Arguments are the volume-level tensors of a `FewshotRegReader` eval item: nested lists `[way][shot]` of support images
     [S,1,H,W] and foreground masks [S,H,W] (background = 1 - foreground), query images [S,1,H,W], the approximate (affine) labels
@@ -120,12 +144,26 @@ class VolumeSegmenter:
                   where a border is empty); the two small tables cross to the host once per volume.  Nothing else changes: mask,
                   counts and dice are those of surface=False.
       surface_out (int64 [2, K-1, 6], float64 [2, K-1, 2]) on the net's device (needs surface=True and query_labels): the rows are
-                  written there, nothing crosses to the host for them and the result's `surface` is None."""
+                  written there, nothing crosses to the host for them and the result's `surface` is None.
+      keep_largest  False, True (connectivity 6), 6 or 26: once the volume is complete, every foreground class of the final mask is
+                  filtered to its largest connected component (rpnet_amd.components.keep_largest) into a SECOND uint8 volume.  mask,
+                  counts, dice and surface of the result stay those of keep_largest=False; the result's `post` is a dict:
+                    'mask'        uint8 [S,H,W] on the device: the filtered mask
+                    'counts'      int64 [K-1, 3] on the host, |P and T|, |P|, |T| of the filtered classes (None without query_labels)
+                    'dice'        per class, dice_from_counts of those (None without query_labels)
+                    'components'  per class {'n_components', 'kept', 'removed'} (voxels)
+                    'surface'     with surface=True and query_labels: per class {'hd95', 'hd', 'assd'} of the filtered mask against
+                                  the labels (one more surface_tally per class), else None
+                  The small tables cross to the host once per volume.
+      post_out    (counts int64 [K-1, 3], stats int64 [K-1, 4]) and, with surface=True, a third member (int64 [K-1, 6],
+                  float64 [K-1, 2]) on the net's device (needs keep_largest and query_labels): the counts are ADDED and the other rows
+                  written there, nothing crosses to the host and every entry of `post` but 'mask' is None."""
 
-    def __init__(self, net, batch=8, graphed=True, surface=False):
+    def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.net, self.batch, self.graphed, self.surface = net.eval(), int(batch), bool(graphed), bool(surface)
+        self.keep_largest = CC.connectivity_of(keep_largest)
         self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
         if self._graphed_eval is not None and self._graphed_eval.net is not net:
             raise ValueError("VolumeSegmenter: the GraphedEval handed in wraps another net")
@@ -176,7 +214,35 @@ class VolumeSegmenter:
         figures = SF.surface_figures(itab.cpu().numpy(), ftab.cpu().numpy())
         return {"fewshot": figures[:K - 1], "affine": figures[K - 1:]}
 
-    def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None):
+    def _post(self, mask, labels, K, post_out):
+        """the final mask filtered to the largest component of every foreground class, and what is measured on it"""
+        dev = mask.device
+        with_surface = self.surface and labels is not None
+        if post_out is not None:
+            counts, stats = post_out[:2]
+            surf = post_out[2] if with_surface else None
+        else:
+            counts = torch.zeros((K - 1, CC.COUNTS_ROW), device=dev, dtype=torch.int64) if labels is not None else None
+            stats = torch.zeros((K - 1, CC.STATS_ROW), device=dev, dtype=torch.int64)
+            surf = (torch.zeros((K - 1, SF.IROW), device=dev, dtype=torch.int64),
+                    torch.zeros((K - 1, SF.FROW), device=dev, dtype=torch.float64)) if with_surface else None
+        kept = torch.empty_like(mask)
+        CC.keep_largest(mask, classes=range(1, K), connectivity=self.keep_largest, truth=labels, out=kept, counts=counts, stats=stats)
+        if with_surface:
+            for c in range(1, K):
+                SF.surface_tally(kept, labels, surf[0], c - 1, surf[1], c - 1, cls=c)
+        post = {"mask": kept, "counts": None, "dice": None, "components": None, "surface": None}
+        if post_out is None:
+            post["components"] = CC.components_figures(stats.cpu().numpy())
+            if counts is not None:
+                post["counts"] = counts.cpu().numpy()
+                post["dice"] = dice_from_counts(post["counts"])
+            if with_surface:
+                post["surface"] = SF.surface_figures(surf[0].cpu().numpy(), surf[1].cpu().numpy())
+        return post
+
+    def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None,
+                 post_out=None):
         dev = next(self.net.parameters()).device
         n_ways, n_shots = len(support_images), len(support_images[0])
         S, B = query_images.shape[0], self.batch
@@ -196,6 +262,15 @@ class VolumeSegmenter:
             check_surface_out(surface_out, K)
             if any(t.device != dev for t in surface_out):
                 raise ValueError(f"surface_out is on {surface_out[0].device}, the net on {dev}")
+        if post_out is not None:
+            if not self.keep_largest:
+                raise ValueError("post_out needs VolumeSegmenter(keep_largest=True, 6 or 26)")
+            if query_labels is None:
+                raise ValueError("post_out needs query_labels (there is nothing to tally without the ground truth)")
+            check_post_out(post_out, K, self.surface)
+            flat = list(post_out[:2]) + (list(post_out[2]) if self.surface else [])
+            if any(t.device != dev for t in flat):
+                raise ValueError(f"post_out is on {next(t.device for t in flat if t.device != dev)}, the net on {dev}")
         nb = -(-S // B)
         pad = nb * B - S
 
@@ -235,6 +310,7 @@ class VolumeSegmenter:
                 seg_tally(tab[2] + [appr[sl]], [0] * (T + 1) + [1], self._nv, labels[sl] if labels is not None else None, counts,
                           mask[sl], mask_src=T, K=K, _table=tab)
             surface = self._surface(mask[:S], appr[:S], labels[:S], K, surface_out) if self.surface and labels is not None else None
+            post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out) if self.keep_largest else None
         if counts is None or counts_out is not None:
             res = VolumeResult(mask[:S], None, None)
         else:
@@ -245,4 +321,6 @@ class VolumeSegmenter:
             res = VolumeResult(mask[:S], host, dice)
         if surface is not None:
             res.surface = surface
+        if post is not None:
+            res.post = post
         return res

@@ -5,7 +5,7 @@ iteration), using only the symbols that driver imports, at the reference's impor
 The reference file itself cannot run offline (it needs tensorboard and the private data).
 
     python tools/eval_driver.py --yaml yamls/example.yml [--items 2] [--on-device] [--device-items] [--batch 8] [--save-pred DIR]
-                                [--surface]
+                                [--surface] [--keep-largest [6|26]]
 
 --on-device: the same lines from rpnet_amd.volume.VolumeSegmenter (masks and Dice tallies on the device, one transfer per volume,
 `--batch` slices per model call through the captured graph); --save-pred DIR writes each volume's predicted mask as
@@ -15,7 +15,10 @@ launch and the registration launches per item) and the tallies and both image si
 once, after the last volume (rpnet_amd.dataset_eval.evaluate_dataset).  --surface (implies --on-device; works with --device-items):
 every item line ends with ` hd95 <fewshot> (<affine>) assd <fewshot> (<affine>)`, the 95th-percentile Hausdorff and the average
 symmetric surface distance of the final mask and of the affine baseline in voxels (rpnet_amd.surface), every class line with their
-means.
+means.  --keep-largest [6|26] (implies --on-device; works with --device-items and --surface; 6 when no number is given): every
+volume's final mask is also filtered to the largest connected component of its class on the device (rpnet_amd.components) and every
+item line ends with ` lcc <dice> (<n_components> components, <removed> voxels removed)`, followed by ` lcc hd95 <v> assd <v>` under
+--surface, every class line with their means; --save-pred then writes the filtered mask.
 """
 import argparse
 import os
@@ -72,17 +75,25 @@ def evaluate(net, loader, config, n_items=None, batch_size=2):
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
-def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None, surface=False):
+def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None, surface=False,
+                       keep_largest=False):
     """`evaluate` through rpnet_amd.volume.VolumeSegmenter: the same printed lines and return value; thresholds, Dice tallies and the
     predicted mask are formed on the device, the tallies cross to the host once per volume.  save_pred: a directory that receives
     every volume's mask as <pid>_<class>.nrrd; segmenter: a VolumeSegmenter to reuse (its captured graphs live with it); surface: the
-    lines gain the surface distances of rpnet_amd.surface (a segmenter handed in must have been made with surface=True)."""
+    lines gain the surface distances of rpnet_amd.surface (a segmenter handed in must have been made with surface=True); keep_largest
+    (False, True = 6, 6 or 26): the lines gain the figures of the mask filtered to its largest component (rpnet_amd.components), and
+    save_pred writes that mask (a segmenter handed in must have been made with the same keep_largest)."""
+    from rpnet_amd import components as CC
     from rpnet_amd import surface as SF
     from rpnet_amd.utils import nrrd
     from rpnet_amd.volume import VolumeSegmenter
-    seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed, surface=surface)
+    conn = CC.connectivity_of(keep_largest)
+    seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed, surface=surface, keep_largest=conn or False)
     if surface and not seg.surface:
         raise ValueError("evaluate_on_device(surface=True) needs a VolumeSegmenter(surface=True)")
+    if conn and seg.keep_largest != conn:
+        raise ValueError(f"evaluate_on_device(keep_largest={conn}) needs a VolumeSegmenter(keep_largest={conn})")
+    lcc_dice, lcc_fig, lcc_surf = defaultdict(list), defaultdict(list), defaultdict(list)
     surf_few, surf_aff = defaultdict(list), defaultdict(list)
     classes = config["eval_classes"]
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
@@ -106,17 +117,26 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
             surf_few[name].append(few)
             surf_aff[name].append(aff)
             line += SF.line_suffix(few, aff)
+        if conn:
+            d_lcc, fig = res.post["dice"][0], res.post["components"][0]
+            kept = res.post["surface"][0] if surface else None
+            lcc_dice[name].append(d_lcc)
+            lcc_fig[name].append(fig)
+            lcc_surf[name].append(kept)
+            line += CC.line_suffix(d_lcc, fig, kept)
         print(line)
         if save_pred:
-            nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), res.mask.cpu().numpy(), encoding="gzip")
+            nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), (res.post["mask"] if conn else res.mask).cpu().numpy(),
+                       encoding="gzip")
     for name in classes:
         if dsc_fewshot[name]:
             print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
-                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else ""))
+                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else "")
+                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None) if conn else ""))
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--yaml", default="yamls/example.yml")
     ap.add_argument("--items", type=int, default=None)
@@ -127,7 +147,14 @@ def main():
                     help="build the items on the device too and fetch all tallies once (rpnet_amd.dataset_eval); implies --on-device")
     ap.add_argument("--surface", action="store_true",
                     help="HD95 and ASSD of the final mask and the affine baseline at the end of every line (rpnet_amd.surface); implies --on-device")
-    a = ap.parse_args()
+    ap.add_argument("--keep-largest", type=int, nargs="?", const=6, default=0, choices=(6, 26), metavar="6|26",
+                    help="also keep only the largest connected component of the final mask (connectivity 6 or 26, 6 when no number is "
+                         "given) and print its figures at the end of every line (rpnet_amd.components); implies --on-device")
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     config, args = load_yaml(a.yaml)
     config["n_iter_refinement"] = config["n_test_iter_refinement"]            # test_rpnet.py:51
     loader = None if a.device_items else FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
@@ -141,9 +168,10 @@ def main():
         from rpnet_amd.dataset_eval import DeviceEvalSource, evaluate_dataset
         source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device)
         source.warm()
-        evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface)
-    elif a.on_device or a.save_pred or a.surface:
-        evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred, surface=a.surface)
+        evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface,
+                         keep_largest=a.keep_largest or False)
+    elif a.on_device or a.save_pred or a.surface or a.keep_largest:
+        evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred, surface=a.surface, keep_largest=a.keep_largest or False)
     else:
         evaluate(net, loader, config, a.items, a.batch or 2)
 
