@@ -254,3 +254,27 @@ def local_corr_bwd(f1, f2, dcorr, r, df1_add=None, dtype=F64):
     KK = (2 * r + 1) ** 2
     g1, g2 = torch.autograd.grad(_local_corr(f1, f2, r), (f1, f2), _c(dcorr, dtype)[..., :KK])
     return (g1 if df1_add is None else g1 + _c(df1_add, dtype)), g2
+
+
+# ---------------------------------------- convolution weight gradient (autograd of nn.Conv2d wrt weight, include/rpnet_abi.h), NHWC
+def conv_wgrad(x0, x1, dy, taps=9, dilation=1, upsample=0, in_scale=None, in_scale_mode=0, dtype=F64):
+    """dW[cout][cin][kh][kw] = sum over pixels p of A[p + tap][cin] * dy[p][cout], written as that sum: nine shifted slices of the
+    zero-padded input and one einsum each (no torch.nn.grad, no autograd).  A is gathered as the forward gathers it: the sources
+    x0 | x1 [N, h, w, C0 | C1] concatenated along C (x1 None: one source), times in_scale [N, h, w] (mode 1) or 1 - in_scale
+    (mode 2) per SOURCE pixel, then nearest x2 up-sampled (upsample = 1).  dy [N, H, W, cout]; taps 9 (3 x 3, tap spacing
+    max(dilation, 1), zero padding of the same width) or 1 (dW [cout][cin][1][1])."""
+    x = _c(x0, dtype) if x1 is None else torch.cat([_c(x0, dtype), _c(x1, dtype)], -1)
+    dy = _c(dy, dtype)
+    if in_scale_mode:
+        s = _c(in_scale, dtype).reshape(x.shape[:3])[..., None]
+        x = x * (s if in_scale_mode == 1 else 1 - s)
+    if upsample:
+        x = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    N, H, W, _ = dy.shape
+    assert x.shape[:3] == dy.shape[:3]
+    if taps == 1:
+        return torch.einsum("nhwi,nhwo->oi", x, dy)[..., None, None]
+    d = max(int(dilation), 1)
+    xp = F.pad(x, (0, 0, d, d, d, d))
+    return torch.stack([torch.stack([torch.einsum("nhwi,nhwo->oi", xp[:, kh * d:kh * d + H, kw * d:kw * d + W], dy)
+                                     for kw in range(3)], -1) for kh in range(3)], -2)

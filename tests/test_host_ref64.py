@@ -113,3 +113,27 @@ def test_local_corr_outside_the_image_is_exactly_zero():
                     inside = 0 <= y + c - r < h and 0 <= x + a - r < w
                     assert inside or (out[:, y, x, a, c] == 0.0).all()
                     assert not inside or (out[:, y, x, a, c] != 0.0).all()
+
+
+@pytest.mark.parametrize("taps,dilation,upsample,mode,two", [(9, 1, 0, 0, False), (9, 1, 0, 1, True), (9, 1, 1, 2, False),
+                                                             (9, 2, 0, 0, True), (1, 1, 0, 0, True), (9, 1, 1, 0, True)])
+def test_conv_wgrad_is_autograd_of_conv2d(taps, dilation, upsample, mode, two):
+    """the pin of R.conv_wgrad (shifted slices and einsum): autograd of F.conv2d in float64 on the same gathered input"""
+    import torch.nn.functional as F
+    N, H, W, C0, C1, Co = 2, 6, 10, 5, 3 if two else 0, 4
+    h, w = H >> upsample, W >> upsample
+    x0, x1 = rnd(901, N, h, w, C0), rnd(902, N, h, w, C1) if two else None
+    dy, s = rnd(903, N, H, W, Co), torch.rand(N, h, w, generator=torch.Generator().manual_seed(904))
+    got = R.conv_wgrad(x0, x1, dy, taps, dilation, upsample, s if mode else None, mode)
+    x = (x0 if x1 is None else torch.cat([x0, x1], -1)).double()
+    if mode:
+        x = x * (s.double() if mode == 1 else 1 - s.double())[..., None]
+    x = x.permute(0, 3, 1, 2)
+    if upsample:
+        x = F.interpolate(x, scale_factor=2, mode="nearest")
+    k = 3 if taps == 9 else 1
+    wt = torch.zeros(Co, C0 + C1, k, k, dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(x, wt, padding=dilation if taps == 9 else 0, dilation=dilation if taps == 9 else 1)
+    (want,) = torch.autograd.grad(y, wt, dy.double().permute(0, 3, 1, 2))
+    assert got.shape == want.shape and rel_err(got, want) < 1e-14
+    assert R.conv_wgrad(x0, x1, dy, taps, dilation, upsample, s if mode else None, mode, dtype=torch.float32).dtype == torch.float32
