@@ -140,16 +140,20 @@ def _cc_fmt(v):
     return "None" if v is None else f"{v:.4f}"
 
 
-def line_suffix(dice, figures, surface=None):
+def _cc_unit(v, unit):
+    return _cc_fmt(v) + (unit if v is not None else "")
+
+
+def line_suffix(dice, figures, surface=None, unit=""):
     """what an item line gains: ` lcc <dice> (<n_components> components, <removed> voxels removed)`, then ` lcc hd95 <v> assd <v>`
-    where the surface distances of the filtered mask were measured"""
+    where the surface distances of the filtered mask were measured (each followed by `unit`: `mm` under a voxel spacing)"""
     s = f" lcc {dice} ({figures['n_components']} components, {figures['removed']} voxels removed)"
     if surface is not None:
-        s += f" lcc hd95 {_cc_fmt(surface['hd95'])} assd {_cc_fmt(surface['assd'])}"
+        s += f" lcc hd95 {_cc_unit(surface['hd95'], unit)} assd {_cc_unit(surface['assd'], unit)}"
     return s
 
 
-def mean_suffix(dices, figures, surfaces=None):
+def mean_suffix(dices, figures, surfaces=None, unit=""):
     """what a class line gains: the same figures as means over the items (Dice and distances over the items where they are not None)"""
     def mean(vals):
         vals = [v for v in vals if v is not None]
@@ -157,5 +161,5 @@ def mean_suffix(dices, figures, surfaces=None):
     s = (f" lcc {_cc_fmt(mean(dices))} ({np.mean([f['n_components'] for f in figures]):.2f} components, "
          f"{np.mean([f['removed'] for f in figures]):.2f} voxels removed)")
     if surfaces is not None:
-        s += f" lcc hd95 {_cc_fmt(mean([r['hd95'] for r in surfaces]))} assd {_cc_fmt(mean([r['assd'] for r in surfaces]))}"
+        s += f" lcc hd95 {_cc_unit(mean([r['hd95'] for r in surfaces]), unit)} assd {_cc_unit(mean([r['assd'] for r in surfaces]), unit)}"
     return s

@@ -24,6 +24,7 @@ from . import components as CC
 from . import hip
 from . import registration as R
 from . import surface as SF
+from . import surface_spacing as SS
 from .hip import call, ptr
 from .utils.volume_reader import FewshotVolumeReader
 from .volume import VolumeSegmenter, dice_from_counts
@@ -164,7 +165,21 @@ class DeviceEvalSource:
                 "supp_pids": [(c, s)], "registration_field": field}
 
 
-def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False):
+def item_spacings(source, n, spacing):
+    """the spacing of each of the first n items: None, one triple for all, or "header": every item's from the NRRD header of its query
+    volume (FewshotVolumeReader.volume_spacing), all read here, before any item is built"""
+    if spacing is None:
+        return [None] * n
+    if isinstance(spacing, str):
+        if spacing != "header":
+            raise ValueError(f'evaluate_dataset: spacing is None, "header" or (sz, sy, sx), got {spacing!r}')
+        rd = source.reader
+        return [rd.volume_spacing(rd.data_info[c][qv]["pid"]) for c, qv in rd.indices[:n]]
+    return [SS.check_spacing(spacing, "evaluate_dataset")] * n
+
+
+def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False,
+                     spacing=None, surface_tolerance=None):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -180,26 +195,41 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     [n_items, K-1, 2] table (its surface rows), cross with the others; every item line then ends with
     ` lcc <dice> (<n_components> components, <removed> voxels removed)`, followed by ` lcc hd95 <v> assd <v>` under surface, every class
     line with their means; `out` receives out["post_counts"], out["components"] and, with surface, out["post_surface_i"] and
-    out["post_surface_f"]; save_pred writes the filtered mask.  The three returned dictionaries are the same either way."""
+    out["post_surface_f"]; save_pred writes the filtered mask.  The three returned dictionaries are the same either way.
+    spacing (with surface=True): None (everything above, every printed character included), (sz, sy, sx) for every item, or "header":
+    every item's spacing from the header of its query volume, all headers read before the first item so that a volume without a spacing
+    fails before any GPU work.  The surface tables then have the widths of rpnet_amd.surface_spacing (int64 [.., 5], fp64 [.., 5]) and
+    arrive as out["surface_mm_i"], out["surface_mm_f"] (and out["post_surface_mm_i"], out["post_surface_mm_f"]), out["spacing"] holds
+    the spacings used; the surface fields of every line are in millimetres and followed by `mm`.  surface_tolerance: the NSD tolerance
+    in millimetres (needs a spacing); the lines then gain ` nsd <fewshot> (<affine>)`."""
     from .utils import nrrd
     conn = CC.connectivity_of(keep_largest)
-    seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False)
     classes = config["eval_classes"]
     n = len(source) if n_items is None else min(n_items, len(source))
+    if (spacing is not None or surface_tolerance is not None) and not surface:
+        raise ValueError("evaluate_dataset: spacing and surface_tolerance act on the surface distances; give surface=True")
+    if surface_tolerance is not None and spacing is None:
+        raise ValueError("evaluate_dataset: surface_tolerance is a distance in millimetres; give spacing= as well")
+    spacings = item_spacings(source, n, spacing)
+    mm = spacing is not None
+    WI, WF = (SS.IROW, SS.FROW) if mm else (SF.IROW, SF.FROW)
+    seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False, surface_tolerance=surface_tolerance)
     dev = next(net.parameters()).device
     T, K = net.num_iter, 2
     table = torch.zeros((n, T + 2, K - 1, 3), device=dev, dtype=torch.int64)
     ncc = torch.zeros((n, 2), device=dev, dtype=torch.float64)
-    surf_i = torch.zeros((n, 2, K - 1, SF.IROW), device=dev, dtype=torch.int64) if surface else None
-    surf_f = torch.zeros((n, 2, K - 1, SF.FROW), device=dev, dtype=torch.float64) if surface else None
+    surf_i = torch.zeros((n, 2, K - 1, WI), device=dev, dtype=torch.int64) if surface else None
+    surf_f = torch.zeros((n, 2, K - 1, WF), device=dev, dtype=torch.float64) if surface else None
     post_c = torch.zeros((n, K - 1, CC.COUNTS_ROW), device=dev, dtype=torch.int64) if conn else None
     post_s = torch.zeros((n, K - 1, CC.STATS_ROW), device=dev, dtype=torch.int64) if conn else None
-    post_i = torch.zeros((n, K - 1, SF.IROW), device=dev, dtype=torch.int64) if conn and surface else None
-    post_f = torch.zeros((n, K - 1, SF.FROW), device=dev, dtype=torch.float64) if conn and surface else None
+    post_i = torch.zeros((n, K - 1, WI), device=dev, dtype=torch.int64) if conn and surface else None
+    post_f = torch.zeros((n, K - 1, WF), device=dev, dtype=torch.float64) if conn and surface else None
     meta, masks = [], []
     for j in range(n):
         s = source.item(j)
         extra = {"surface_out": (surf_i[j], surf_f[j])} if surface else {}
+        if mm:
+            extra["spacing"] = spacings[j]
         if conn:
             extra["post_out"] = (post_c[j], post_s[j]) + (((post_i[j], post_f[j]),) if surface else ())
         res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j],
@@ -215,7 +245,10 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     if surface:
         surf_i, surf_f = surf_i.cpu().numpy(), surf_f.cpu().numpy()
         if out is not None:
-            out["surface_i"], out["surface_f"] = surf_i, surf_f
+            if mm:
+                out["surface_mm_i"], out["surface_mm_f"], out["spacing"] = surf_i, surf_f, list(spacings)
+            else:
+                out["surface_i"], out["surface_f"] = surf_i, surf_f
     lcc_dice, lcc_fig, lcc_surf = defaultdict(list), defaultdict(list), defaultdict(list)
     if conn:
         post_c, post_s = post_c.cpu().numpy(), post_s.cpu().numpy()
@@ -224,7 +257,7 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
         if surface:
             post_i, post_f = post_i.cpu().numpy(), post_f.cpu().numpy()
             if out is not None:
-                out["post_surface_i"], out["post_surface_f"] = post_i, post_f
+                out["post_surface_mm_i" if mm else "post_surface_i"], out["post_surface_mm_f" if mm else "post_surface_f"] = post_i, post_f
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
     if save_pred:
         os.makedirs(save_pred, exist_ok=True)
@@ -238,23 +271,27 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             dsc_ref[name][k].append(d)
             line += f" ref {k} {d},"
         if surface:
-            few, aff = SF.surface_figures(surf_i[j, :, 0], surf_f[j, :, 0])
+            few, aff = (SS.spacing_figures(surf_i[j, :, 0], surf_f[j, :, 0], surface_tolerance) if mm
+                        else SF.surface_figures(surf_i[j, :, 0], surf_f[j, :, 0]))
             surf_few[name].append(few)
             surf_aff[name].append(aff)
-            line += SF.line_suffix(few, aff)
+            line += SS.line_suffix_mm(few, aff, surface_tolerance is not None) if mm else SF.line_suffix(few, aff)
         if conn:
             d_lcc, fig = dice_from_counts(post_c[j])[0], CC.components_figures(post_s[j])[0]
-            kept = SF.surface_figures(post_i[j], post_f[j])[0] if surface else None
+            kept = None
+            if surface:
+                kept = SS.spacing_figures(post_i[j], post_f[j], surface_tolerance)[0] if mm else SF.surface_figures(post_i[j], post_f[j])[0]
             lcc_dice[name].append(d_lcc)
             lcc_fig[name].append(fig)
             lcc_surf[name].append(kept)
-            line += CC.line_suffix(d_lcc, fig, kept)
+            line += CC.line_suffix(d_lcc, fig, kept, unit="mm" if mm else "")
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
     for name in classes:
         if dsc_fewshot[name]:
             print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
-                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else "")
-                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None) if conn else ""))
+                  + ((SS.mean_suffix_mm(surf_few[name], surf_aff[name], surface_tolerance is not None) if mm
+                      else SF.mean_suffix(surf_few[name], surf_aff[name])) if surface else "")
+                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else ""))
     return dsc_affine, dsc_fewshot, dsc_ref

@@ -189,6 +189,16 @@ _CC_SIGS = {
 CC_ABI_SYMBOLS = tuple(_CC_SIGS)
 CC_ABI_VERSION = 1     # RPNET_CC_ABI_VERSION of include/rpnet_cc_abi.h
 
+# surface distances on a grid with a per-axis voxel spacing: include/rpnet_surface_spacing_abi.h (additions beside the six headers above;
+# their ledger is tests/surface_spacing_abi_ledger.py)
+_SURFACE_SPACING_SIGS = {
+    "rpnet_surface_spacing_abi_version": (ci, []),
+    "rpnet_surface_spacing_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_surface_spacing_tally": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, C.POINTER(cd), cd, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+SURFACE_SPACING_ABI_SYMBOLS = tuple(_SURFACE_SPACING_SIGS)
+SURFACE_SPACING_ABI_VERSION = 1     # RPNET_SURFACE_SPACING_ABI_VERSION of include/rpnet_surface_spacing_abi.h
+
 
 def lib_path():
     return _LIB_PATH
@@ -207,7 +217,7 @@ def load():
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
         for name, (res, args) in (list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()) + list(_GUARD_SIGS.items())
-                                  + list(_SURFACE_SIGS.items()) + list(_CC_SIGS.items())):
+                                  + list(_SURFACE_SIGS.items()) + list(_CC_SIGS.items()) + list(_SURFACE_SPACING_SIGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
@@ -227,6 +237,10 @@ def load():
         if lib.rpnet_cc_abi_version() != CC_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has connected-component ABI version {lib.rpnet_cc_abi_version()}, this binding was written "
                                f"for {CC_ABI_VERSION} (include/rpnet_cc_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
+        if lib.rpnet_surface_spacing_abi_version() != SURFACE_SPACING_ABI_VERSION:
+            raise RuntimeError(f"{_LIB_PATH} has surface-spacing ABI version {lib.rpnet_surface_spacing_abi_version()}, this binding was "
+                               f"written for {SURFACE_SPACING_ABI_VERSION} (include/rpnet_surface_spacing_abi.h): rebuild it with "
+                               "`make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

@@ -9,6 +9,9 @@ With unit spacing every squared distance is an integer, so the device forms ever
 `surface_tally` leaves one int64 row {n_A, n_B, d2_k, d2_k1, d2_max, k} and one fp64 row {sum_A sqrt(d2), sum_B sqrt(d2)} in tables
 that stay on the device; `surface_from_rows` turns a pair of rows into the three figures on the host; `surface_reference` restates
 the definition in numpy and is what the GPU tests compare with (tests/test_host_surface.py pins it to scipy.ndimage).
+
+Millimetres on a grid with a per-axis voxel spacing, and the normalised surface Dice: rpnet_amd.surface_spacing (a float64 transform
+and a radix selection beside this integer path, which stays the yardstick for it at spacing (1, 1, 1)).
 """
 import math
 

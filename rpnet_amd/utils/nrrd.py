@@ -87,6 +87,12 @@ def _dtype(header):
     return np.dtype(("<" if endian == "little" else ">") + code)
 
 
+def read_header(filename):
+    """-> header, the dict `read` returns beside the data, without reading or decoding the payload"""
+    with open(filename, "rb") as f:
+        return _parse_header(f)
+
+
 def read(filename):
     """-> (data, header); data.shape == header['sizes'] (first axis fastest in the file), native byte order."""
     with open(filename, "rb") as f:

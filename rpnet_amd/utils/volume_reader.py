@@ -246,6 +246,17 @@ class FewshotVolumeReader(torch.utils.data.Dataset):
         y1, y2 = max(0, H // 2 - ny // 2), min(H, H // 2 + ny // 2)
         return image[:self.cfg["num_slice"], y1:y2, x1:x2]
 
+    def volume_spacing(self, pid):
+        """(sz, sy, sx): the voxel spacing of the axes [D, H, W] of volume `pid`, from the header of `<pid>_clean.nrrd` alone (the
+        payload is not read).  Truncation, padding, the annotated z range and the crop change no spacing, so axis i of the file is
+        axis i of every tensor made from it.  ValueError when the header carries none."""
+        from ..surface_spacing import spacing_from_header
+        path = os.path.join(self.data_dir, f"{pid}_clean.nrrd")
+        try:
+            return spacing_from_header(nrrd.read_header(path))
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+
     def load_image_and_mask(self, filename, roi_name):
         m, _ = nrrd.read(os.path.join(self.data_dir, f"{filename}_{roi_name}.nrrd"))
         mask = pad2factor(self.truncate_image(m.astype(np.float32)), factor=16, pad_value=0)[None, ...]
@@ -391,10 +402,15 @@ def train_collate(batch):
 
 
 # ------------------------------------------------------------------------------------------ synthetic NRRD data set
-def write_synthetic_dataset(root, n_volumes=3, classes=("Liver",), shape=(22, 44, 40), seed=0):
+def write_synthetic_dataset(root, n_volumes=3, classes=("Liver",), shape=(22, 44, 40), seed=0, spacing=None):
     """A tiny data set in the reference's on-disk layout (for tests and demos): `<pid>_clean.nrrd` int16 HU volumes
     [D,H,W], `<pid>_<roi>.nrrd` uint8 masks, `<root>/split/all.csv` (one pid per line) and
-    `<root>/split/classes/<roi>.csv` (pid, z_start, z_end).  Returns (data_dir, set_name, class_csv_dir)."""
+    `<root>/split/classes/<roi>.csv` (pid, z_start, z_end).  Returns (data_dir, set_name, class_csv_dir).  spacing: a triple
+    (sz, sy, sx) written as `space directions` into both files of a volume; None writes no spatial field."""
+    extra = None
+    if spacing is not None:
+        sz, sy, sx = (float(v) for v in spacing)
+        extra = {"space": "left-posterior-superior", "space directions": f"({sz!r},0,0) (0,{sy!r},0) (0,0,{sx!r})"}
     rng = np.random.default_rng(seed)
     data_dir, split = os.path.join(root, "data"), os.path.join(root, "split")
     os.makedirs(data_dir, exist_ok=True)
@@ -411,11 +427,11 @@ def write_synthetic_dataset(root, n_volumes=3, classes=("Liver",), shape=(22, 44
             rz, ry, rx = D * rng.uniform(0.25, 0.35), H * rng.uniform(0.15, 0.25), W * rng.uniform(0.15, 0.25)
             organ = ((zz - cz) / rz) ** 2 + ((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1
             vol = np.where(organ, 110.0 + 25 * r + rng.normal(0, 8, shape), vol)
-            nrrd.write(os.path.join(data_dir, f"{pid}_{roi}.nrrd"), organ.astype(np.uint8))
+            nrrd.write(os.path.join(data_dir, f"{pid}_{roi}.nrrd"), organ.astype(np.uint8), header=extra)
             zs = np.nonzero(organ.any(axis=(1, 2)))[0]
             rows[roi].append((pid, int(zs.min()), int(zs.max())))
         vol[rng.random(shape) > 0.9995] = 3500.0                        # a few metal-like outliers above the HU window
-        nrrd.write(os.path.join(data_dir, f"{pid}_clean.nrrd"), np.clip(vol, -1024, 4000).astype(np.int16))
+        nrrd.write(os.path.join(data_dir, f"{pid}_clean.nrrd"), np.clip(vol, -1024, 4000).astype(np.int16), header=extra)
     set_name = os.path.join(split, "all.csv")
     with open(set_name, "w") as f:
         f.write("\n".join(pids) + "\n")

@@ -17,6 +17,7 @@ import torch
 from . import components as CC
 from . import hip
 from . import surface as SF
+from . import surface_spacing as SS
 from .graph import GraphedEval
 
 
@@ -75,22 +76,32 @@ def seg_tally(sources, kinds, n_valid, labels=None, counts=None, mask=None, mask
              mask_src, N, K, H, W)
 
 
-def check_surface_out(surface_out, K):
-    """the tables of surface rows a caller hands to VolumeSegmenter: (int64 [2, K-1, 6], float64 [2, K-1, 2]), both contiguous: rows of
-    the final mask, then of the affine baseline, per foreground class"""
+def surface_widths(spacing):
+    """(columns of an int64 surface row, columns of an fp64 one): those of rpnet_amd.surface, or of rpnet_amd.surface_spacing under a
+    spacing"""
+    return (SF.IROW, SF.FROW) if spacing is None else (SS.IROW, SS.FROW)
+
+
+def check_surface_out(surface_out, K, spacing=None):
+    """the tables of surface rows a caller hands to VolumeSegmenter: (int64 [2, K-1, 6], float64 [2, K-1, 2]), under a spacing (int64
+    [2, K-1, 5], float64 [2, K-1, 5]), both contiguous: rows of the final mask, then of the affine baseline, per foreground class"""
+    wi, wf = surface_widths(spacing)
     ok = isinstance(surface_out, (tuple, list)) and len(surface_out) == 2 and all(torch.is_tensor(t) and t.is_contiguous() for t in surface_out)
     if ok:
         it, ft = surface_out
-        ok = (it.dtype == torch.int64 and tuple(it.shape) == (2, K - 1, SF.IROW) and ft.dtype == torch.float64
-              and tuple(ft.shape) == (2, K - 1, SF.FROW))
+        ok = (it.dtype == torch.int64 and tuple(it.shape) == (2, K - 1, wi) and ft.dtype == torch.float64
+              and tuple(ft.shape) == (2, K - 1, wf))
     if not ok:
-        raise ValueError(f"surface_out must be a pair of contiguous tensors (int64 [2, {K - 1}, {SF.IROW}], float64 [2, {K - 1}, {SF.FROW}]): "
+        under = "" if spacing is None else " (the widths under a spacing: rpnet_amd.surface_spacing)"
+        raise ValueError(f"surface_out must be a pair of contiguous tensors (int64 [2, {K - 1}, {wi}], float64 [2, {K - 1}, {wf}]){under}: "
                          "the rows of the final mask and of the affine baseline per foreground class")
 
 
-def check_post_out(post_out, K, surface):
+def check_post_out(post_out, K, surface, spacing=None):
     """the tables a caller hands to VolumeSegmenter(keep_largest=...): (counts int64 [K-1, 3], stats int64 [K-1, 4]) and, with
-    surface=True, a third member (int64 [K-1, 6], float64 [K-1, 2]); all contiguous: one row per foreground class of the filtered mask"""
+    surface=True, a third member (int64 [K-1, 6], float64 [K-1, 2]), under a spacing (int64 [K-1, 5], float64 [K-1, 5]); all
+    contiguous: one row per foreground class of the filtered mask"""
+    wi, wf = surface_widths(spacing)
     want = 3 if surface else 2
     ok = isinstance(post_out, (tuple, list)) and len(post_out) == want and all(torch.is_tensor(t) and t.is_contiguous() for t in post_out[:2])
     if ok:
@@ -100,11 +111,12 @@ def check_post_out(post_out, K, surface):
     if ok and surface:
         pair = post_out[2]
         ok = isinstance(pair, (tuple, list)) and len(pair) == 2 and all(torch.is_tensor(t) and t.is_contiguous() for t in pair)
-        ok = ok and (pair[0].dtype == torch.int64 and tuple(pair[0].shape) == (K - 1, SF.IROW) and pair[1].dtype == torch.float64
-                     and tuple(pair[1].shape) == (K - 1, SF.FROW))
+        ok = ok and (pair[0].dtype == torch.int64 and tuple(pair[0].shape) == (K - 1, wi) and pair[1].dtype == torch.float64
+                     and tuple(pair[1].shape) == (K - 1, wf))
     if not ok:
         raise ValueError(f"post_out must be contiguous tensors (int64 [{K - 1}, {CC.COUNTS_ROW}], int64 [{K - 1}, {CC.STATS_ROW}]"
-                         + (f", (int64 [{K - 1}, {SF.IROW}], float64 [{K - 1}, {SF.FROW}])" if surface else "")
+                         + (f", (int64 [{K - 1}, {wi}], float64 [{K - 1}, {wf}])" if surface else "")
+                         + (" (the widths under a spacing)" if surface and spacing is not None else "")
                          + "): the Dice counts, the component statistics" + (" and the surface rows" if surface else "")
                          + " of the filtered mask per foreground class")
 
@@ -120,8 +132,9 @@ def check_counts_out(counts_out, K, T=None):
 
 
 class VolumeSegmenter:
-    """`VolumeSegmenter(net, batch=8, graphed=True, surface=False, keep_largest=False)(support_images, support_fg, query_images,
-    appr_query_labels, query_labels=None, counts_out=None, surface_out=None, post_out=None)` -> VolumeResult(mask, counts, dice).
+    """`VolumeSegmenter(net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None)(
+    support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None, post_out=None,
+    spacing=None)` -> VolumeResult(mask, counts, dice).
 
     Arguments are the volume-level tensors of a `FewshotRegReader` eval item: nested lists `[way][shot]` of support images
     [S,1,H,W] and foreground masks [S,H,W] (background = 1 - foreground), query images [S,1,H,W], the approximate (affine) labels
@@ -145,6 +158,12 @@ class VolumeSegmenter:
                   counts and dice are those of surface=False.
       surface_out (int64 [2, K-1, 6], float64 [2, K-1, 2]) on the net's device (needs surface=True and query_labels): the rows are
                   written there, nothing crosses to the host for them and the result's `surface` is None.
+      spacing     None (the integer path above, untouched), or (sz, sy, sx): the voxel spacing of the axes [S, H, W], here or per call
+                  (a call's spacing wins).  With surface=True the tallies are rpnet_amd.surface_spacing.surface_tally_spacing: the
+                  figures are {'hd95', 'hd', 'assd', 'nsd'} in the unit of the spacing (millimetres), surface_out and the third
+                  member of post_out take the widths of that module (int64 [.., 5], float64 [.., 5]), and the final mask, the affine
+                  baseline and the filtered mask all go through it.
+      surface_tolerance  the NSD tolerance in the unit of the spacing (None: 'nsd' is None); needs a spacing.
       keep_largest  False, True (connectivity 6), 6 or 26: once the volume is complete, every foreground class of the final mask is
                   filtered to its largest connected component (rpnet_amd.components.keep_largest) into a SECOND uint8 volume.  mask,
                   counts, dice and surface of the result stay those of keep_largest=False; the result's `post` is a dict:
@@ -159,9 +178,13 @@ class VolumeSegmenter:
                   float64 [K-1, 2]) on the net's device (needs keep_largest and query_labels): the counts are ADDED and the other rows
                   written there, nothing crosses to the host and every entry of `post` but 'mask' is None."""
 
-    def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False):
+    def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None):
         if batch < 1:
             raise ValueError("batch must be >= 1")
+        self.spacing = None if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
+        self.surface_tolerance = None if surface_tolerance is None else float(surface_tolerance)
+        if self.surface_tolerance is not None and not self.surface_tolerance >= 0:
+            raise ValueError(f"VolumeSegmenter: surface_tolerance must be a number >= 0, got {surface_tolerance!r}")
         self.net, self.batch, self.graphed, self.surface = net.eval(), int(batch), bool(graphed), bool(surface)
         self.keep_largest = CC.connectivity_of(keep_largest)
         self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
@@ -197,26 +220,39 @@ class VolumeSegmenter:
         tab[0][len(tab[2])] = appr.data_ptr()
         return tab
 
-    def _surface(self, mask, appr, labels, K, surface_out):
+    def _tally(self, pred, labels, it, ft, row, cls, spacing):
+        if spacing is None:
+            SF.surface_tally(pred, labels, it, row, ft, row, cls=cls)
+        else:
+            SS.surface_tally_spacing(pred, labels, spacing, it, row, ft, row, cls=cls, tau=self.surface_tolerance)
+
+    def _figures(self, itab, ftab, spacing):
+        if spacing is None:
+            return SF.surface_figures(itab.cpu().numpy(), ftab.cpu().numpy())
+        return SS.spacing_figures(itab.cpu().numpy(), ftab.cpu().numpy(), self.surface_tolerance)
+
+    def _surface(self, mask, appr, labels, K, surface_out, spacing=None):
         """the rows of the final mask (0) and the affine baseline (1) against the labels, per foreground class"""
         dev = mask.device
+        wi, wf = surface_widths(spacing)
         if surface_out is not None:
             itab, ftab = surface_out
         else:
-            itab = torch.zeros((2, K - 1, SF.IROW), device=dev, dtype=torch.int64)
-            ftab = torch.zeros((2, K - 1, SF.FROW), device=dev, dtype=torch.float64)
-        it, ft = itab.view(-1, SF.IROW), ftab.view(-1, SF.FROW)
+            itab = torch.zeros((2, K - 1, wi), device=dev, dtype=torch.int64)
+            ftab = torch.zeros((2, K - 1, wf), device=dev, dtype=torch.float64)
+        it, ft = itab.view(-1, wi), ftab.view(-1, wf)
         for s, pred in enumerate((mask, appr)):
             for c in range(1, K):
-                SF.surface_tally(pred, labels, it, s * (K - 1) + c - 1, ft, s * (K - 1) + c - 1, cls=c)
+                self._tally(pred, labels, it, ft, s * (K - 1) + c - 1, c, spacing)
         if surface_out is not None:
             return None
-        figures = SF.surface_figures(itab.cpu().numpy(), ftab.cpu().numpy())
+        figures = self._figures(itab, ftab, spacing)
         return {"fewshot": figures[:K - 1], "affine": figures[K - 1:]}
 
-    def _post(self, mask, labels, K, post_out):
+    def _post(self, mask, labels, K, post_out, spacing=None):
         """the final mask filtered to the largest component of every foreground class, and what is measured on it"""
         dev = mask.device
+        wi, wf = surface_widths(spacing)
         with_surface = self.surface and labels is not None
         if post_out is not None:
             counts, stats = post_out[:2]
@@ -224,13 +260,13 @@ class VolumeSegmenter:
         else:
             counts = torch.zeros((K - 1, CC.COUNTS_ROW), device=dev, dtype=torch.int64) if labels is not None else None
             stats = torch.zeros((K - 1, CC.STATS_ROW), device=dev, dtype=torch.int64)
-            surf = (torch.zeros((K - 1, SF.IROW), device=dev, dtype=torch.int64),
-                    torch.zeros((K - 1, SF.FROW), device=dev, dtype=torch.float64)) if with_surface else None
+            surf = (torch.zeros((K - 1, wi), device=dev, dtype=torch.int64),
+                    torch.zeros((K - 1, wf), device=dev, dtype=torch.float64)) if with_surface else None
         kept = torch.empty_like(mask)
         CC.keep_largest(mask, classes=range(1, K), connectivity=self.keep_largest, truth=labels, out=kept, counts=counts, stats=stats)
         if with_surface:
             for c in range(1, K):
-                SF.surface_tally(kept, labels, surf[0], c - 1, surf[1], c - 1, cls=c)
+                self._tally(kept, labels, surf[0], surf[1], c - 1, c, spacing)
         post = {"mask": kept, "counts": None, "dice": None, "components": None, "surface": None}
         if post_out is None:
             post["components"] = CC.components_figures(stats.cpu().numpy())
@@ -238,12 +274,15 @@ class VolumeSegmenter:
                 post["counts"] = counts.cpu().numpy()
                 post["dice"] = dice_from_counts(post["counts"])
             if with_surface:
-                post["surface"] = SF.surface_figures(surf[0].cpu().numpy(), surf[1].cpu().numpy())
+                post["surface"] = self._figures(surf[0], surf[1], spacing)
         return post
 
     def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None,
-                 post_out=None):
+                 post_out=None, spacing=None):
         dev = next(self.net.parameters()).device
+        spacing = self.spacing if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
+        if self.surface_tolerance is not None and spacing is None and self.surface:
+            raise ValueError("VolumeSegmenter: surface_tolerance is a distance in the unit of a spacing; give spacing= as well")
         n_ways, n_shots = len(support_images), len(support_images[0])
         S, B = query_images.shape[0], self.batch
         H, W = query_images.shape[-2:]
@@ -259,7 +298,7 @@ class VolumeSegmenter:
                 raise ValueError("surface_out needs VolumeSegmenter(surface=True)")
             if query_labels is None:
                 raise ValueError("surface_out needs query_labels (a surface distance is measured against the ground truth)")
-            check_surface_out(surface_out, K)
+            check_surface_out(surface_out, K, spacing)
             if any(t.device != dev for t in surface_out):
                 raise ValueError(f"surface_out is on {surface_out[0].device}, the net on {dev}")
         if post_out is not None:
@@ -267,7 +306,7 @@ class VolumeSegmenter:
                 raise ValueError("post_out needs VolumeSegmenter(keep_largest=True, 6 or 26)")
             if query_labels is None:
                 raise ValueError("post_out needs query_labels (there is nothing to tally without the ground truth)")
-            check_post_out(post_out, K, self.surface)
+            check_post_out(post_out, K, self.surface, spacing)
             flat = list(post_out[:2]) + (list(post_out[2]) if self.surface else [])
             if any(t.device != dev for t in flat):
                 raise ValueError(f"post_out is on {next(t.device for t in flat if t.device != dev)}, the net on {dev}")
@@ -309,8 +348,8 @@ class VolumeSegmenter:
                     nv_now = n_valid
                 seg_tally(tab[2] + [appr[sl]], [0] * (T + 1) + [1], self._nv, labels[sl] if labels is not None else None, counts,
                           mask[sl], mask_src=T, K=K, _table=tab)
-            surface = self._surface(mask[:S], appr[:S], labels[:S], K, surface_out) if self.surface and labels is not None else None
-            post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out) if self.keep_largest else None
+            surface = self._surface(mask[:S], appr[:S], labels[:S], K, surface_out, spacing) if self.surface and labels is not None else None
+            post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out, spacing) if self.keep_largest else None
         if counts is None or counts_out is not None:
             res = VolumeResult(mask[:S], None, None)
         else:

@@ -5,7 +5,7 @@ iteration), using only the symbols that driver imports, at the reference's impor
 The reference file itself cannot run offline (it needs tensorboard and the private data).
 
     python tools/eval_driver.py --yaml yamls/example.yml [--items 2] [--on-device] [--device-items] [--batch 8] [--save-pred DIR]
-                                [--surface] [--keep-largest [6|26]]
+                                [--surface] [--keep-largest [6|26]] [--spacing header|Z,Y,X] [--surface-tolerance MM]
 
 --on-device: the same lines from rpnet_amd.volume.VolumeSegmenter (masks and Dice tallies on the device, one transfer per volume,
 `--batch` slices per model call through the captured graph); --save-pred DIR writes each volume's predicted mask as
@@ -18,7 +18,10 @@ symmetric surface distance of the final mask and of the affine baseline in voxel
 means.  --keep-largest [6|26] (implies --on-device; works with --device-items and --surface; 6 when no number is given): every
 volume's final mask is also filtered to the largest connected component of its class on the device (rpnet_amd.components) and every
 item line ends with ` lcc <dice> (<n_components> components, <removed> voxels removed)`, followed by ` lcc hd95 <v> assd <v>` under
---surface, every class line with their means; --save-pred then writes the filtered mask.
+--surface, every class line with their means; --save-pred then writes the filtered mask.  --spacing header|Z,Y,X and
+--surface-tolerance MM (both imply --surface; the yaml keys surface_spacing and surface_tolerance are their defaults): the surface
+distances in millimetres on the voxel spacing of every query volume's NRRD header, or on one given spacing (rpnet_amd.surface_spacing),
+each figure followed by `mm`, and with a tolerance the normalised surface Dice ` nsd <fewshot> (<affine>)`.
 """
 import argparse
 import os
@@ -75,20 +78,47 @@ def evaluate(net, loader, config, n_items=None, batch_size=2):
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
+def parse_spacing(value):
+    """None, "header" or a triple of floats from the command line / the yaml: `header`, `Z,Y,X` or a list of three numbers"""
+    if value is None or value == "header":
+        return value
+    parts = value.split(",") if isinstance(value, str) else list(value)
+    try:
+        triple = tuple(float(v) for v in parts)
+    except (TypeError, ValueError):
+        triple = ()
+    if len(triple) != 3:
+        raise ValueError(f"--spacing / surface_spacing: `header` or three numbers Z,Y,X, got {value!r}")
+    return triple
+
+
 def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None, surface=False,
-                       keep_largest=False):
+                       keep_largest=False, spacing=None, surface_tolerance=None):
     """`evaluate` through rpnet_amd.volume.VolumeSegmenter: the same printed lines and return value; thresholds, Dice tallies and the
     predicted mask are formed on the device, the tallies cross to the host once per volume.  save_pred: a directory that receives
     every volume's mask as <pid>_<class>.nrrd; segmenter: a VolumeSegmenter to reuse (its captured graphs live with it); surface: the
     lines gain the surface distances of rpnet_amd.surface (a segmenter handed in must have been made with surface=True); keep_largest
     (False, True = 6, 6 or 26): the lines gain the figures of the mask filtered to its largest component (rpnet_amd.components), and
-    save_pred writes that mask (a segmenter handed in must have been made with the same keep_largest)."""
+    save_pred writes that mask (a segmenter handed in must have been made with the same keep_largest).  spacing (None, "header" or a
+    triple) and surface_tolerance: the surface figures in millimetres, as evaluate_dataset prints them; "header" reads the header of
+    every query volume before the first item."""
     from rpnet_amd import components as CC
     from rpnet_amd import surface as SF
+    from rpnet_amd import surface_spacing as SS
     from rpnet_amd.utils import nrrd
     from rpnet_amd.volume import VolumeSegmenter
     conn = CC.connectivity_of(keep_largest)
-    seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed, surface=surface, keep_largest=conn or False)
+    if surface_tolerance is not None and spacing is None:
+        raise ValueError("evaluate_on_device: surface_tolerance is a distance in millimetres; give spacing= as well")
+    seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed, surface=surface, keep_largest=conn or False,
+                                       surface_tolerance=surface_tolerance)
+    n_loop = len(loader) if n_items is None else min(n_items, len(loader))
+    mm, nsd = spacing is not None, surface_tolerance is not None
+    if spacing == "header":
+        rd = loader.fewshot_reader.fewshot_volume_reader
+        spacings = [rd.volume_spacing(rd.data_info[c][qv]["pid"]) for c, qv in rd.indices[:n_loop]]
+    else:
+        spacings = [spacing] * n_loop
     if surface and not seg.surface:
         raise ValueError("evaluate_on_device(surface=True) needs a VolumeSegmenter(surface=True)")
     if conn and seg.keep_largest != conn:
@@ -99,9 +129,10 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
     if save_pred:
         os.makedirs(save_pred, exist_ok=True)
-    for j in range(len(loader) if n_items is None else min(n_items, len(loader))):
+    for j in range(n_loop):
         s = loader[j]
-        res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"])
+        res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"],
+                  **({"spacing": spacings[j]} if mm else {}))
         name = classes[s["class_id"]]
         d_aff, d_few = res.dice["affine"][0], res.dice["fewshot"][0]
         with torch.no_grad():
@@ -116,14 +147,14 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
             few, aff = res.surface["fewshot"][0], res.surface["affine"][0]
             surf_few[name].append(few)
             surf_aff[name].append(aff)
-            line += SF.line_suffix(few, aff)
+            line += SS.line_suffix_mm(few, aff, nsd) if mm else SF.line_suffix(few, aff)
         if conn:
             d_lcc, fig = res.post["dice"][0], res.post["components"][0]
             kept = res.post["surface"][0] if surface else None
             lcc_dice[name].append(d_lcc)
             lcc_fig[name].append(fig)
             lcc_surf[name].append(kept)
-            line += CC.line_suffix(d_lcc, fig, kept)
+            line += CC.line_suffix(d_lcc, fig, kept, unit="mm" if mm else "")
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), (res.post["mask"] if conn else res.mask).cpu().numpy(),
@@ -131,8 +162,9 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
     for name in classes:
         if dsc_fewshot[name]:
             print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
-                  + (SF.mean_suffix(surf_few[name], surf_aff[name]) if surface else "")
-                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None) if conn else ""))
+                  + ((SS.mean_suffix_mm(surf_few[name], surf_aff[name], nsd) if mm else SF.mean_suffix(surf_few[name], surf_aff[name]))
+                     if surface else "")
+                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else ""))
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
@@ -150,6 +182,12 @@ def build_parser():
     ap.add_argument("--keep-largest", type=int, nargs="?", const=6, default=0, choices=(6, 26), metavar="6|26",
                     help="also keep only the largest connected component of the final mask (connectivity 6 or 26, 6 when no number is "
                          "given) and print its figures at the end of every line (rpnet_amd.components); implies --on-device")
+    ap.add_argument("--spacing", default=None, metavar="header|Z,Y,X",
+                    help="surface distances in millimetres: the voxel spacing of every query volume's NRRD header, or one spacing for "
+                         "all (rpnet_amd.surface_spacing); implies --surface; default: the yaml key surface_spacing")
+    ap.add_argument("--surface-tolerance", type=float, default=None, metavar="MM",
+                    help="also the normalised surface Dice at this tolerance in millimetres; implies --surface and needs a spacing; "
+                         "default: the yaml key surface_tolerance")
     return ap
 
 
@@ -157,6 +195,9 @@ def main():
     a = build_parser().parse_args()
     config, args = load_yaml(a.yaml)
     config["n_iter_refinement"] = config["n_test_iter_refinement"]            # test_rpnet.py:51
+    spacing = parse_spacing(a.spacing if a.spacing is not None else config.get("surface_spacing"))
+    tolerance = a.surface_tolerance if a.surface_tolerance is not None else config.get("surface_tolerance")
+    a.surface = a.surface or spacing is not None or tolerance is not None
     loader = None if a.device_items else FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
     net = model_factory[args.net](pretrained_path=config.get("pretrained_path"),
                                   cfg={"align": True, "backbone": config.get("backbone", "vgg")}, backbone_cfg=config).cuda()
@@ -169,9 +210,10 @@ def main():
         source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device)
         source.warm()
         evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface,
-                         keep_largest=a.keep_largest or False)
+                         keep_largest=a.keep_largest or False, spacing=spacing, surface_tolerance=tolerance)
     elif a.on_device or a.save_pred or a.surface or a.keep_largest:
-        evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred, surface=a.surface, keep_largest=a.keep_largest or False)
+        evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred, surface=a.surface, keep_largest=a.keep_largest or False,
+                           spacing=spacing, surface_tolerance=tolerance)
     else:
         evaluate(net, loader, config, a.items, a.batch or 2)
 
