@@ -21,6 +21,7 @@ import torch
 
 from . import augment as A
 from . import components as CC
+from . import postprocess as PP
 from . import hip
 from . import registration as R
 from . import surface as SF
@@ -179,7 +180,7 @@ def item_spacings(source, n, spacing):
 
 
 def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False,
-                     spacing=None, surface_tolerance=None):
+                     spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None, min_component=None):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -201,43 +202,61 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     fails before any GPU work.  The surface tables then have the widths of rpnet_amd.surface_spacing (int64 [.., 5], fp64 [.., 5]) and
     arrive as out["surface_mm_i"], out["surface_mm_f"] (and out["post_surface_mm_i"], out["post_surface_mm_f"]), out["spacing"] holds
     the spacings used; the surface fields of every line are in millimetres and followed by `mm`.  surface_tolerance: the NSD tolerance
-    in millimetres (needs a spacing); the lines then gain ` nsd <fewshot> (<affine>)`."""
+    in millimetres (needs a spacing); the lines then gain ` nsd <fewshot> (<affine>)`.
+    fill_holes (False, True or "3d", "slice"), hole_connectivity, max_hole, min_component (voxels, or (mm3, "mm3") under a spacing, with
+    "header" resolved per item; a spacing is then accepted without surface=True): the clean-up chain of VolumeSegmenter, remove small ->
+    keep largest -> fill holes (rpnet_amd.postprocess).  One more device table, int64 [n_items, K-1, 8] (columns 0..3 the statistics row
+    of fill_holes, 4..7 that of remove_small, zeros for a stage that is off), crosses with the others and arrives as out["post_stats"];
+    the tables named under keep_largest then describe the end of the chain (out["components"] only with keep_largest); every item line
+    gains ` holes <n> (<filled> voxels filled)` and ` small <n> (<removed> voxels removed)` for the stages that are on, after the lcc
+    figures, every class line their means; save_pred writes the end of the chain.  With these options off nothing changes."""
     from .utils import nrrd
+    from .volume import check_min_component
     conn = CC.connectivity_of(keep_largest)
+    holes_on, small_min = PP.holes_mode_of(fill_holes) is not None, check_min_component(min_component)
+    small_on = small_min is not None
+    chain = bool(conn) or holes_on or small_on
+    mm3 = isinstance(small_min, tuple)
+    if mm3 and spacing is None:
+        raise ValueError("evaluate_dataset: min_component in mm3 needs a spacing (a triple or 'header')")
     classes = config["eval_classes"]
     n = len(source) if n_items is None else min(n_items, len(source))
-    if (spacing is not None or surface_tolerance is not None) and not surface:
+    if ((spacing is not None and not mm3) or surface_tolerance is not None) and not surface:
         raise ValueError("evaluate_dataset: spacing and surface_tolerance act on the surface distances; give surface=True")
     if surface_tolerance is not None and spacing is None:
         raise ValueError("evaluate_dataset: surface_tolerance is a distance in millimetres; give spacing= as well")
     spacings = item_spacings(source, n, spacing)
     mm = spacing is not None
     WI, WF = (SS.IROW, SS.FROW) if mm else (SF.IROW, SF.FROW)
-    seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False, surface_tolerance=surface_tolerance)
+    seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False, surface_tolerance=surface_tolerance,
+                          fill_holes=fill_holes, hole_connectivity=hole_connectivity, max_hole=max_hole, min_component=min_component)
     dev = next(net.parameters()).device
     T, K = net.num_iter, 2
     table = torch.zeros((n, T + 2, K - 1, 3), device=dev, dtype=torch.int64)
     ncc = torch.zeros((n, 2), device=dev, dtype=torch.float64)
     surf_i = torch.zeros((n, 2, K - 1, WI), device=dev, dtype=torch.int64) if surface else None
     surf_f = torch.zeros((n, 2, K - 1, WF), device=dev, dtype=torch.float64) if surface else None
-    post_c = torch.zeros((n, K - 1, CC.COUNTS_ROW), device=dev, dtype=torch.int64) if conn else None
-    post_s = torch.zeros((n, K - 1, CC.STATS_ROW), device=dev, dtype=torch.int64) if conn else None
-    post_i = torch.zeros((n, K - 1, WI), device=dev, dtype=torch.int64) if conn and surface else None
-    post_f = torch.zeros((n, K - 1, WF), device=dev, dtype=torch.float64) if conn and surface else None
+    post_c = torch.zeros((n, K - 1, CC.COUNTS_ROW), device=dev, dtype=torch.int64) if chain else None
+    post_s = torch.zeros((n, K - 1, CC.STATS_ROW), device=dev, dtype=torch.int64) if chain else None
+    post_i = torch.zeros((n, K - 1, WI), device=dev, dtype=torch.int64) if chain and surface else None
+    post_f = torch.zeros((n, K - 1, WF), device=dev, dtype=torch.float64) if chain and surface else None
+    post_w = torch.zeros((n, K - 1, 2 * PP.STATS_ROW), device=dev, dtype=torch.int64) if holes_on or small_on else None
     meta, masks = [], []
     for j in range(n):
         s = source.item(j)
         extra = {"surface_out": (surf_i[j], surf_f[j])} if surface else {}
         if mm:
             extra["spacing"] = spacings[j]
-        if conn:
+        if chain:
             extra["post_out"] = (post_c[j], post_s[j]) + (((post_i[j], post_f[j]),) if surface else ())
+        if post_w is not None:
+            extra["post_stats_out"] = post_w[j]
         res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j],
                   **extra)
         ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
         meta.append((s["pid"], classes[s["class_id"]]))
         if save_pred:
-            masks.append(res.post["mask"] if conn else res.mask)
+            masks.append(res.post["mask"] if chain else res.mask)
     counts, ncc = table.cpu().numpy(), ncc.cpu().numpy()          # the two transfers of the data set
     if out is not None:
         out["counts"], out["ncc"] = counts, ncc
@@ -250,10 +269,17 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             else:
                 out["surface_i"], out["surface_f"] = surf_i, surf_f
     lcc_dice, lcc_fig, lcc_surf = defaultdict(list), defaultdict(list), defaultdict(list)
-    if conn:
+    holes_fig, small_fig = defaultdict(list), defaultdict(list)
+    if chain:
         post_c, post_s = post_c.cpu().numpy(), post_s.cpu().numpy()
         if out is not None:
-            out["post_counts"], out["components"] = post_c, post_s
+            out["post_counts"] = post_c
+            if conn:
+                out["components"] = post_s
+        if post_w is not None:
+            post_w = post_w.cpu().numpy()
+            if out is not None:
+                out["post_stats"] = post_w
         if surface:
             post_i, post_f = post_i.cpu().numpy(), post_f.cpu().numpy()
             if out is not None:
@@ -285,6 +311,12 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             lcc_fig[name].append(fig)
             lcc_surf[name].append(kept)
             line += CC.line_suffix(d_lcc, fig, kept, unit="mm" if mm else "")
+        if post_w is not None:
+            h = PP.holes_figures(post_w[j, :, :PP.STATS_ROW])[0] if holes_on else None
+            sm = PP.small_figures(post_w[j, :, PP.STATS_ROW:])[0] if small_on else None
+            holes_fig[name].append(h)
+            small_fig[name].append(sm)
+            line += PP.line_suffix(h, sm)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
@@ -293,5 +325,6 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
                   + ((SS.mean_suffix_mm(surf_few[name], surf_aff[name], surface_tolerance is not None) if mm
                       else SF.mean_suffix(surf_few[name], surf_aff[name])) if surface else "")
-                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else ""))
+                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else "")
+                  + (PP.mean_suffix(holes_fig[name] if holes_on else None, small_fig[name] if small_on else None) if post_w is not None else ""))
     return dsc_affine, dsc_fewshot, dsc_ref

@@ -199,6 +199,17 @@ _SURFACE_SPACING_SIGS = {
 SURFACE_SPACING_ABI_SYMBOLS = tuple(_SURFACE_SPACING_SIGS)
 SURFACE_SPACING_ABI_VERSION = 1     # RPNET_SURFACE_SPACING_ABI_VERSION of include/rpnet_surface_spacing_abi.h
 
+# hole filling and the small-component filter of an evaluated volume: include/rpnet_ccpost_abi.h (additions beside the seven headers
+# above; their ledger is tests/ccpost_abi_ledger.py)
+_CCPOST_SIGS = {
+    "rpnet_ccpost_abi_version": (ci, []),
+    "rpnet_ccpost_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_ccpost_fill_holes": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, C.c_int64, vp, ci, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+    "rpnet_ccpost_remove_small": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, C.c_int64, vp, ci, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+CCPOST_ABI_SYMBOLS = tuple(_CCPOST_SIGS)
+CCPOST_ABI_VERSION = 1     # RPNET_CCPOST_ABI_VERSION of include/rpnet_ccpost_abi.h
+
 
 def lib_path():
     return _LIB_PATH
@@ -217,7 +228,8 @@ def load():
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
         for name, (res, args) in (list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()) + list(_GUARD_SIGS.items())
-                                  + list(_SURFACE_SIGS.items()) + list(_CC_SIGS.items()) + list(_SURFACE_SPACING_SIGS.items())):
+                                  + list(_SURFACE_SIGS.items()) + list(_CC_SIGS.items()) + list(_SURFACE_SPACING_SIGS.items())
+                                  + list(_CCPOST_SIGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
@@ -241,6 +253,9 @@ def load():
             raise RuntimeError(f"{_LIB_PATH} has surface-spacing ABI version {lib.rpnet_surface_spacing_abi_version()}, this binding was "
                                f"written for {SURFACE_SPACING_ABI_VERSION} (include/rpnet_surface_spacing_abi.h): rebuild it with "
                                "`make -C rpnet_amd/csrc`")
+        if lib.rpnet_ccpost_abi_version() != CCPOST_ABI_VERSION:
+            raise RuntimeError(f"{_LIB_PATH} has post-processing ABI version {lib.rpnet_ccpost_abi_version()}, this binding was written "
+                               f"for {CCPOST_ABI_VERSION} (include/rpnet_ccpost_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

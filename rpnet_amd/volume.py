@@ -12,10 +12,12 @@ import ctypes as C
 import weakref
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import components as CC
 from . import hip
+from . import postprocess as PP
 from . import surface as SF
 from . import surface_spacing as SS
 from .graph import GraphedEval
@@ -131,6 +133,20 @@ def check_counts_out(counts_out, K, T=None):
                          f"got {tuple(counts_out.shape)}")
 
 
+def check_min_component(min_component):
+    """the `min_component` option -> None (off), an int (voxels, at least 1) or (mm3, 'mm3'), resolved under a call's spacing"""
+    if min_component is None or min_component is False:
+        return None
+    if isinstance(min_component, (tuple, list)) and len(min_component) == 2 and min_component[1] == "mm3":
+        v = float(min_component[0])
+        if not (v >= 0 and np.isfinite(v)):
+            raise ValueError(f"min_component: the volume in mm3 must be a finite number >= 0, got {min_component[0]!r}")
+        return (v, "mm3")
+    if isinstance(min_component, (int, np.integer)) and not isinstance(min_component, bool) and int(min_component) >= 1:
+        return int(min_component)
+    raise ValueError(f"min_component must be None, a number of voxels >= 1 or (mm3, 'mm3'), got {min_component!r}")
+
+
 class VolumeSegmenter:
     """`VolumeSegmenter(net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None)(
     support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None, post_out=None,
@@ -176,9 +192,25 @@ class VolumeSegmenter:
                   The small tables cross to the host once per volume.
       post_out    (counts int64 [K-1, 3], stats int64 [K-1, 4]) and, with surface=True, a third member (int64 [K-1, 6],
                   float64 [K-1, 2]) on the net's device (needs keep_largest and query_labels): the counts are ADDED and the other rows
-                  written there, nothing crosses to the host and every entry of `post` but 'mask' is None."""
+                  written there, nothing crosses to the host and every entry of `post` but 'mask' is None.
+      fill_holes  False, True or '3d' (the holes of the volume), 'slice' (every slice on its own): the holes of every foreground class
+                  are filled (rpnet_amd.postprocess.fill_holes; with the one foreground class of an evaluation this is
+                  scipy.ndimage.binary_fill_holes).  hole_connectivity: of the background, None (6, per slice 4), 6 or 26, per slice 4
+                  or 8.  max_hole: the largest hole in voxels that is filled (None: no bound).
+      min_component  None, a number of voxels, or (mm3, 'mm3') under a spacing (rpnet_amd.postprocess.min_voxels_from_mm3): the
+                  components of every foreground class with fewer voxels are removed (rpnet_amd.postprocess.remove_small, under the
+                  connectivity of keep_largest, 6 without it).
+                  The chain on the final mask is fixed: remove small -> keep largest -> fill holes, each stage reading the output of
+                  the one before.  With any stage on, post['mask'], 'counts', 'dice' and 'surface' describe the end of the chain,
+                  'components' is None without keep_largest, and `post` gains 'small' and 'holes': per class the figures of
+                  postprocess.small_figures / holes_figures (None for a stage that is off).  With both options off nothing changes.
+                  post_out is accepted with any stage on and keeps its shape rules; its statistics table [K-1, 4] belongs to keep_largest and
+                  is left as it is without that stage.
+      post_stats_out  int64 [K-1, 8] on the net's device (needs post_out): columns 0..3 take the statistics row of fill_holes, 4..7 that
+                  of remove_small (the columns of a stage that is off are left as they are); 'holes' and 'small' of `post` are None."""
 
-    def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None):
+    def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None, fill_holes=False,
+                 hole_connectivity=None, max_hole=None, min_component=None):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.spacing = None if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
@@ -187,6 +219,14 @@ class VolumeSegmenter:
             raise ValueError(f"VolumeSegmenter: surface_tolerance must be a number >= 0, got {surface_tolerance!r}")
         self.net, self.batch, self.graphed, self.surface = net.eval(), int(batch), bool(graphed), bool(surface)
         self.keep_largest = CC.connectivity_of(keep_largest)
+        self.fill_holes = PP.holes_mode_of(fill_holes)          # None: off, False: 3D, True: per slice
+        if self.fill_holes is None and (hole_connectivity is not None or max_hole is not None):
+            raise ValueError("VolumeSegmenter: hole_connectivity and max_hole need fill_holes")
+        self.hole_connectivity = None if self.fill_holes is None else PP.hole_connectivity_of(hole_connectivity, self.fill_holes)
+        if max_hole is not None and int(max_hole) < 1:
+            raise ValueError(f"VolumeSegmenter: max_hole must be None (no bound) or at least 1 voxel, got {max_hole!r}")
+        self.max_hole = None if max_hole is None else int(max_hole)
+        self.min_component = check_min_component(min_component)
         self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
         if self._graphed_eval is not None and self._graphed_eval.net is not net:
             raise ValueError("VolumeSegmenter: the GraphedEval handed in wraps another net")
@@ -249,8 +289,9 @@ class VolumeSegmenter:
         figures = self._figures(itab, ftab, spacing)
         return {"fewshot": figures[:K - 1], "affine": figures[K - 1:]}
 
-    def _post(self, mask, labels, K, post_out, spacing=None):
-        """the final mask filtered to the largest component of every foreground class, and what is measured on it"""
+    def _post(self, mask, labels, K, post_out, spacing=None, post_stats_out=None):
+        """the clean-up chain on the final mask (remove small -> keep largest -> fill holes, each stage that is on), and what is
+        measured at its end.  Only the last stage tallies the Dice counts: they describe the end of the chain."""
         dev = mask.device
         wi, wf = surface_widths(spacing)
         with_surface = self.surface and labels is not None
@@ -263,13 +304,43 @@ class VolumeSegmenter:
             surf = (torch.zeros((K - 1, wi), device=dev, dtype=torch.int64),
                     torch.zeros((K - 1, wf), device=dev, dtype=torch.float64)) if with_surface else None
         kept = torch.empty_like(mask)
-        CC.keep_largest(mask, classes=range(1, K), connectivity=self.keep_largest, truth=labels, out=kept, counts=counts, stats=stats)
+        stages = [name for name, on in (("small", self.min_component is not None), ("largest", bool(self.keep_largest)),
+                                        ("holes", self.fill_holes is not None)) if on]
+        tables, src = {}, mask
+        for name in stages:
+            last = name == stages[-1]
+            tally = dict(truth=labels if last else None, out=kept, counts=counts if last else None)
+            if name == "small":
+                m = self.min_component
+                if isinstance(m, tuple):
+                    if spacing is None:
+                        raise ValueError("VolumeSegmenter: min_component in mm3 needs a spacing")
+                    m = PP.min_voxels_from_mm3(m[0], spacing)
+                tables[name] = PP.remove_small(src, range(1, K), m, connectivity=self.keep_largest or 6, **tally)[2]
+            elif name == "largest":
+                CC.keep_largest(src, classes=range(1, K), connectivity=self.keep_largest, stats=stats, **tally)
+            else:
+                tables[name] = PP.fill_holes(src, range(1, K), connectivity=self.hole_connectivity, per_slice=self.fill_holes,
+                                             max_hole=self.max_hole, **tally)[2]
+            src = kept                  # the later stages work in place on the output of the first
         if with_surface:
             for c in range(1, K):
                 self._tally(kept, labels, surf[0], surf[1], c - 1, c, spacing)
+        if post_stats_out is not None:
+            for at, name in ((0, "holes"), (PP.STATS_ROW, "small")):
+                if name in tables:
+                    post_stats_out[:, at:at + PP.STATS_ROW].copy_(tables[name])
         post = {"mask": kept, "counts": None, "dice": None, "components": None, "surface": None}
+        extended = stages != ["largest"]
+        if extended:
+            post.update(holes=None, small=None)
         if post_out is None:
-            post["components"] = CC.components_figures(stats.cpu().numpy())
+            if self.keep_largest:
+                post["components"] = CC.components_figures(stats.cpu().numpy())
+            if "holes" in tables:
+                post["holes"] = PP.holes_figures(tables["holes"].cpu().numpy())
+            if "small" in tables:
+                post["small"] = PP.small_figures(tables["small"].cpu().numpy())
             if counts is not None:
                 post["counts"] = counts.cpu().numpy()
                 post["dice"] = dice_from_counts(post["counts"])
@@ -278,8 +349,9 @@ class VolumeSegmenter:
         return post
 
     def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None,
-                 post_out=None, spacing=None):
+                 post_out=None, spacing=None, post_stats_out=None):
         dev = next(self.net.parameters()).device
+        chain = bool(self.keep_largest) or self.fill_holes is not None or self.min_component is not None
         spacing = self.spacing if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
         if self.surface_tolerance is not None and spacing is None and self.surface:
             raise ValueError("VolumeSegmenter: surface_tolerance is a distance in the unit of a spacing; give spacing= as well")
@@ -302,14 +374,22 @@ class VolumeSegmenter:
             if any(t.device != dev for t in surface_out):
                 raise ValueError(f"surface_out is on {surface_out[0].device}, the net on {dev}")
         if post_out is not None:
-            if not self.keep_largest:
-                raise ValueError("post_out needs VolumeSegmenter(keep_largest=True, 6 or 26)")
+            if not chain:
+                raise ValueError("post_out needs VolumeSegmenter(keep_largest=True, 6 or 26, fill_holes=... or min_component=...)")
             if query_labels is None:
                 raise ValueError("post_out needs query_labels (there is nothing to tally without the ground truth)")
             check_post_out(post_out, K, self.surface, spacing)
             flat = list(post_out[:2]) + (list(post_out[2]) if self.surface else [])
             if any(t.device != dev for t in flat):
                 raise ValueError(f"post_out is on {next(t.device for t in flat if t.device != dev)}, the net on {dev}")
+        if post_stats_out is not None:
+            if post_out is None or (self.fill_holes is None and self.min_component is None):
+                raise ValueError("post_stats_out needs post_out and VolumeSegmenter(fill_holes=... or min_component=...)")
+            if not (torch.is_tensor(post_stats_out) and post_stats_out.dtype == torch.int64 and post_stats_out.is_contiguous()
+                    and tuple(post_stats_out.shape) == (K - 1, 2 * PP.STATS_ROW)):
+                raise ValueError(f"post_stats_out must be a contiguous int64 [{K - 1}, {2 * PP.STATS_ROW}] tensor")
+            if post_stats_out.device != dev:
+                raise ValueError(f"post_stats_out is on {post_stats_out.device}, the net on {dev}")
         nb = -(-S // B)
         pad = nb * B - S
 
@@ -349,7 +429,7 @@ class VolumeSegmenter:
                 seg_tally(tab[2] + [appr[sl]], [0] * (T + 1) + [1], self._nv, labels[sl] if labels is not None else None, counts,
                           mask[sl], mask_src=T, K=K, _table=tab)
             surface = self._surface(mask[:S], appr[:S], labels[:S], K, surface_out, spacing) if self.surface and labels is not None else None
-            post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out, spacing) if self.keep_largest else None
+            post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out, spacing, post_stats_out) if chain else None
         if counts is None or counts_out is not None:
             res = VolumeResult(mask[:S], None, None)
         else:

@@ -92,8 +92,22 @@ def parse_spacing(value):
     return triple
 
 
+def parse_min_component(value):
+    """--min-component: None, a number of voxels, or `<x>mm3` -> (x, "mm3"), which needs a spacing"""
+    if value is None:
+        return None
+    text = str(value).strip()
+    try:
+        if text.lower().endswith("mm3"):
+            return (float(text[:-3]), "mm3")
+        return int(text)
+    except ValueError:
+        raise ValueError(f"--min-component: a number of voxels or <x>mm3, got {value!r}") from None
+
+
 def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None, surface=False,
-                       keep_largest=False, spacing=None, surface_tolerance=None):
+                       keep_largest=False, spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None,
+                       min_component=None):
     """`evaluate` through rpnet_amd.volume.VolumeSegmenter: the same printed lines and return value; thresholds, Dice tallies and the
     predicted mask are formed on the device, the tallies cross to the host once per volume.  save_pred: a directory that receives
     every volume's mask as <pid>_<class>.nrrd; segmenter: a VolumeSegmenter to reuse (its captured graphs live with it); surface: the
@@ -101,8 +115,14 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
     (False, True = 6, 6 or 26): the lines gain the figures of the mask filtered to its largest component (rpnet_amd.components), and
     save_pred writes that mask (a segmenter handed in must have been made with the same keep_largest).  spacing (None, "header" or a
     triple) and surface_tolerance: the surface figures in millimetres, as evaluate_dataset prints them; "header" reads the header of
-    every query volume before the first item."""
+    every query volume before the first item.  fill_holes, hole_connectivity, max_hole, min_component: the clean-up chain of
+    VolumeSegmenter (remove small -> keep largest -> fill holes, rpnet_amd.postprocess); the lines gain ` holes <n> (<filled> voxels
+    filled)` and ` small <n> (<removed> voxels removed)` for the stages that are on, the lcc figures and save_pred describe the end of the
+    chain, and min_component in mm3 is resolved under every item's spacing (a segmenter handed in must have been made with the same
+    options)."""
     from rpnet_amd import components as CC
+    from rpnet_amd import postprocess as PP
+    from rpnet_amd.volume import check_min_component
     from rpnet_amd import surface as SF
     from rpnet_amd import surface_spacing as SS
     from rpnet_amd.utils import nrrd
@@ -110,8 +130,16 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
     conn = CC.connectivity_of(keep_largest)
     if surface_tolerance is not None and spacing is None:
         raise ValueError("evaluate_on_device: surface_tolerance is a distance in millimetres; give spacing= as well")
+    holes_mode, small_min = PP.holes_mode_of(fill_holes), check_min_component(min_component)
+    holes_on, small_on = holes_mode is not None, small_min is not None
+    chain = bool(conn) or holes_on or small_on
+    if isinstance(small_min, tuple) and spacing is None:
+        raise ValueError("evaluate_on_device: min_component in mm3 needs a spacing (a triple or 'header')")
     seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed, surface=surface, keep_largest=conn or False,
-                                       surface_tolerance=surface_tolerance)
+                                       surface_tolerance=surface_tolerance, fill_holes=fill_holes, hole_connectivity=hole_connectivity,
+                                       max_hole=max_hole, min_component=min_component)
+    if (holes_on or small_on) and (seg.fill_holes != holes_mode or seg.min_component != small_min):
+        raise ValueError("evaluate_on_device(fill_holes=..., min_component=...) needs a VolumeSegmenter made with the same options")
     n_loop = len(loader) if n_items is None else min(n_items, len(loader))
     mm, nsd = spacing is not None, surface_tolerance is not None
     if spacing == "header":
@@ -124,6 +152,7 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
     if conn and seg.keep_largest != conn:
         raise ValueError(f"evaluate_on_device(keep_largest={conn}) needs a VolumeSegmenter(keep_largest={conn})")
     lcc_dice, lcc_fig, lcc_surf = defaultdict(list), defaultdict(list), defaultdict(list)
+    holes_fig, small_fig = defaultdict(list), defaultdict(list)
     surf_few, surf_aff = defaultdict(list), defaultdict(list)
     classes = config["eval_classes"]
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
@@ -155,16 +184,23 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
             lcc_fig[name].append(fig)
             lcc_surf[name].append(kept)
             line += CC.line_suffix(d_lcc, fig, kept, unit="mm" if mm else "")
+        if holes_on or small_on:
+            h, sm = res.post["holes"][0] if holes_on else None, res.post["small"][0] if small_on else None
+            holes_fig[name].append(h)
+            small_fig[name].append(sm)
+            line += PP.line_suffix(h, sm)
         print(line)
         if save_pred:
-            nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), (res.post["mask"] if conn else res.mask).cpu().numpy(),
+            nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), (res.post["mask"] if chain else res.mask).cpu().numpy(),
                        encoding="gzip")
     for name in classes:
         if dsc_fewshot[name]:
             print(f"{name}, affine {np.mean(dsc_affine[name]):.4f}, fewshot {np.mean(dsc_fewshot[name]):.4f}"
                   + ((SS.mean_suffix_mm(surf_few[name], surf_aff[name], nsd) if mm else SF.mean_suffix(surf_few[name], surf_aff[name]))
                      if surface else "")
-                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else ""))
+                  + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else "")
+                  + (PP.mean_suffix(holes_fig[name] if holes_on else None, small_fig[name] if small_on else None)
+                     if holes_on or small_on else ""))
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
@@ -188,6 +224,13 @@ def build_parser():
     ap.add_argument("--surface-tolerance", type=float, default=None, metavar="MM",
                     help="also the normalised surface Dice at this tolerance in millimetres; implies --surface and needs a spacing; "
                          "default: the yaml key surface_tolerance")
+    ap.add_argument("--fill-holes", nargs="?", const="3d", default=None, choices=("3d", "slice"), metavar="3d|slice",
+                    help="fill the holes of the final mask, of the volume (3d, also when no word is given) or of every slice on its own "
+                         "(rpnet_amd.postprocess); implies --on-device")
+    ap.add_argument("--max-hole", type=int, default=None, metavar="VOXELS", help="fill only holes of at most this many voxels; needs --fill-holes")
+    ap.add_argument("--min-component", default=None, metavar="VOXELS|<x>mm3",
+                    help="remove the components of the final mask with fewer voxels, or below <x> cubic millimetres under --spacing (with "
+                         "`header` resolved per item); implies --on-device")
     return ap
 
 
@@ -198,6 +241,12 @@ def main():
     spacing = parse_spacing(a.spacing if a.spacing is not None else config.get("surface_spacing"))
     tolerance = a.surface_tolerance if a.surface_tolerance is not None else config.get("surface_tolerance")
     a.surface = a.surface or spacing is not None or tolerance is not None
+    min_component = parse_min_component(a.min_component)
+    if a.max_hole is not None and a.fill_holes is None:
+        raise SystemExit("--max-hole needs --fill-holes")
+    if isinstance(min_component, tuple) and spacing is None:
+        raise SystemExit("--min-component <x>mm3 needs --spacing")
+    post = dict(fill_holes=a.fill_holes or False, max_hole=a.max_hole, min_component=min_component)
     loader = None if a.device_items else FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
     net = model_factory[args.net](pretrained_path=config.get("pretrained_path"),
                                   cfg={"align": True, "backbone": config.get("backbone", "vgg")}, backbone_cfg=config).cuda()
@@ -210,10 +259,10 @@ def main():
         source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device)
         source.warm()
         evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface,
-                         keep_largest=a.keep_largest or False, spacing=spacing, surface_tolerance=tolerance)
-    elif a.on_device or a.save_pred or a.surface or a.keep_largest:
+                         keep_largest=a.keep_largest or False, spacing=spacing, surface_tolerance=tolerance, **post)
+    elif a.on_device or a.save_pred or a.surface or a.keep_largest or a.fill_holes or min_component is not None:
         evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred, surface=a.surface, keep_largest=a.keep_largest or False,
-                           spacing=spacing, surface_tolerance=tolerance)
+                           spacing=spacing, surface_tolerance=tolerance, **post)
     else:
         evaluate(net, loader, config, a.items, a.batch or 2)
 
