@@ -1,5 +1,5 @@
 // The phases the connected-component entry points (components.hip, include/rpnet_cc_abi.h) and the post-processing entry points
-// (cc_post.hip, include/rpnet_ccpost_abi.h) share: the tile constants, the head of a workspace, the element readers, union-find in LDS
+// (cc_post.hip, include/rpnet_ccpost_abi.h) share: the tile constants, the head of a workspace, union-find in LDS
 // and in global memory, local labelling, the seam merge and flatten + sizes.  The local labelling and the seam merge are templates:
 //   kComplement  the labelled voxels are those with `value != cls` (the background of a class) instead of `value == cls`;
 //   kPlanar      no link has a z component: every z slice is its own 2D image (no z joins inside the tile, no z seams), so
@@ -10,11 +10,10 @@
 
 #include <algorithm>
 
-#include "common.h"
 #include "rpnet_cc_abi.h"
+#include "volume_kinds.h"
 
 namespace rpnet {
-
 
 constexpr int kCcLX = 6, kCcLY = 5, kCcLZ = 2;                  // log2 of the tile extents
 constexpr int kCcTX = 1 << kCcLX, kCcTY = 1 << kCcLY, kCcTZ = 1 << kCcLZ;
@@ -35,22 +34,9 @@ struct CcHead {                         // the first 64 bytes of a workspace, cl
 };
 static_assert(sizeof(CcHead) == kCcHeadBytes && offsetof(CcHead, overrun) == RPNET_CC_OVERRUN_OFFSET, "head layout");
 
-__device__ __forceinline__ bool cc_fg(const void* p, const int kind, const size_t i, const int cls) {
-    switch (kind) {
-        case RPNET_CC_U8: return (int)static_cast<const uint8_t*>(p)[i] == cls;
-        case RPNET_CC_I32: return static_cast<const int32_t*>(p)[i] == cls;
-        case RPNET_CC_I64: return static_cast<const int64_t*>(p)[i] == (int64_t)cls;
-        default: return static_cast<const float*>(p)[i] == (float)cls;
-    }
-}
-__device__ __forceinline__ uint8_t cc_u8(const void* p, const int kind, const size_t i) {
-    switch (kind) {
-        case RPNET_CC_U8: return static_cast<const uint8_t*>(p)[i];
-        case RPNET_CC_I32: return (uint8_t)static_cast<const int32_t*>(p)[i];
-        case RPNET_CC_I64: return (uint8_t)static_cast<const int64_t*>(p)[i];
-        default: return (uint8_t)(int)static_cast<const float*>(p)[i];
-    }
-}
+static_assert(RPNET_CC_U8 == RPNET_SURFACE_U8 && RPNET_CC_I32 == RPNET_SURFACE_I32 && RPNET_CC_I64 == RPNET_SURFACE_I64 &&
+                  RPNET_CC_F32 == RPNET_SURFACE_F32,
+              "vol_fg and vol_u8 of volume_kinds.h switch over the element kinds of both headers");
 
 // is (dz, dy, dx) one of the lower half of the neighbourhood (the neighbours that come before a voxel in z-major order)?
 __host__ __device__ constexpr bool cc_lower(const int dz, const int dy, const int dx) {
@@ -111,7 +97,7 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const void* __restrict__ 
     for (int k = 0; k < kCcTile / 256; ++k) {
         const int l = t + 256 * k;
         const int y = y0 + ((l >> kCcLX) & (kCcTY - 1)), z = z0 + (l >> (kCcLX + kCcLY));
-        const bool f = x < W && y < H && z < D && cc_fg(vol, kind, ((size_t)z * H + y) * W + x, cls) != kComplement;
+        const bool f = x < W && y < H && z < D && vol_fg(vol, kind, ((size_t)z * H + y) * W + x, cls) != kComplement;
         const unsigned long long m = __ballot(f);
         const unsigned long long gaps = ~m & ((1ull << lane) - 1ull);          // background voxels of the row before this one
         const int start = gaps ? 64 - __clzll((long long)gaps) : 0;

@@ -26,15 +26,6 @@ constexpr int kPostLane = 16;                       // voxels of a lane in the a
 static_assert(RPNET_CCPOST_OVERRUN_OFFSET == RPNET_CC_OVERRUN_OFFSET, "the head is that of components.hip");
 static_assert((long long)RPNET_CC_MAX_DIM * RPNET_CC_MAX_DIM * RPNET_CC_MAX_DIM <= (1ll << 30), "a size must leave bit 31 free");
 
-__device__ __forceinline__ bool post_zero(const void* p, const int kind, const size_t i) {
-    switch (kind) {
-        case RPNET_CC_U8: return static_cast<const uint8_t*>(p)[i] == 0;
-        case RPNET_CC_I32: return static_cast<const int32_t*>(p)[i] == 0;
-        case RPNET_CC_I64: return static_cast<const int64_t*>(p)[i] == 0;
-        default: return static_cast<const float*>(p)[i] == 0.0f;
-    }
-}
-
 // Clear.  The head and the size volume are cleared by a launch, not by hipMemsetAsync: captured in a graph, the memset node of such a
 // head has come back with stale bytes on replay (surface_spacing.hip met the same), while a kernel's arguments are part of its node.
 // n16: the 16-byte words of the size volume (its bytes are a multiple of 16 and it starts 16-byte aligned inside the workspace).
@@ -112,7 +103,7 @@ __global__ __launch_bounds__(256) void post_apply_kernel(const void* in, const i
             if (j >= cnt) continue;
             const size_t i = base + j;
             const int p = parent[i];
-            const uint8_t v = cc_u8(in, kind, i);
+            const uint8_t v = vol_u8(in, kind, i);
             bool sel = false;
             if (p >= 0) {
                 if (p != last_p) {
@@ -132,7 +123,7 @@ __global__ __launch_bounds__(256) void post_apply_kernel(const void* in, const i
             }
             bool pred;                              // does the result hold the class here?
             if (kHoles) {
-                const bool fill = sel && post_zero(in, kind, i);
+                const bool fill = sel && vol_fg(in, kind, i, 0);          // only a voxel of value 0 is filled
                 if (fill) ++vox;
                 o.b[j] = fill ? (uint8_t)cls : v;
                 pred = p < 0 || fill;
@@ -141,7 +132,7 @@ __global__ __launch_bounds__(256) void post_apply_kernel(const void* in, const i
                 pred = p >= 0 && !sel;
             }
             if (truth) {
-                const bool tr = cc_fg(truth, truth_kind, i, cls);
+                const bool tr = vol_fg(truth, truth_kind, i, cls);
                 c_pt += pred && tr;
                 c_p += pred;
                 c_t += tr;

@@ -68,10 +68,10 @@ __global__ __launch_bounds__(256) void cc_filter_kernel(const void* in, const in
         const size_t i = ((size_t)blockIdx.x * iters + it) * 256u + t;
         if (i >= n) continue;
         const bool keep = parent[i] == chosen;
-        const uint8_t v = cc_u8(in, kind, i);
-        out[i] = keep ? (uint8_t)cls : (cc_fg(in, kind, i, cls) ? (uint8_t)0 : v);
+        const uint8_t v = vol_u8(in, kind, i);
+        out[i] = keep ? (uint8_t)cls : (vol_fg(in, kind, i, cls) ? (uint8_t)0 : v);
         if (truth) {
-            const bool tr = cc_fg(truth, truth_kind, i, cls);
+            const bool tr = vol_fg(truth, truth_kind, i, cls);
             if (keep && tr) atomicAdd(&sc[0], 1u);
             if (keep) atomicAdd(&sc[1], 1u);
             if (tr) atomicAdd(&sc[2], 1u);

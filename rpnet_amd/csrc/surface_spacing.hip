@@ -1,7 +1,6 @@
 // Surface distances of an evaluated volume on a grid with a per-axis voxel spacing (include/rpnet_surface_spacing_abi.h;
-// rpnet_amd/surface_spacing.py): the tallies behind HD95, HD, ASSD and NSD in millimetres.  The integer path of surface.hip stays as it
-// is; here the squared distance of a voxel is ((wx*dx^2 + wy*dy^2) + wz*dz^2) in fp64, minimised over the border voxels by the same
-// separable min-plus transform.  Every product and every sum is one rounding (__dmul_rn / __dadd_rn, and the file is built with
+// rpnet_amd/surface_spacing.py): the tallies behind HD95, HD, ASSD and NSD in millimetres.  The transform is that of surface.hip
+// (surface_edt.h) under another metric: the squared distance of a voxel is ((wx*dx^2 + wy*dy^2) + wz*dz^2) in fp64.  Every product and every sum is one rounding (__dmul_rn / __dadd_rn, and the file is built with
 // -ffp-contract=off), every squared offset an exact integer, and a minimum does not depend on the order of its candidates: a numpy
 // restatement of the same operations gets the same bits.
 //
@@ -16,19 +15,13 @@
 #include <cfloat>
 #include <cmath>
 
-#include "common.h"
-#include "rpnet_surface_abi.h"
 #include "rpnet_surface_spacing_abi.h"
+#include "surface_edt.h"
 
 namespace rpnet {
 
 typedef unsigned long long sps_u64;
 
-constexpr double kSpsNoSeed = DBL_MAX;                          // finite, above every reachable distance; DBL_MAX + w*o^2 never goes below it
-constexpr int kSpsLineElems = RPNET_SURFACE_SPACING_MAX_DIM;    // voxels a block of the x pass stages (whole lines)
-constexpr int kSpsTileBytes = 32 * 1024;                        // LDS of a y / z tile while its rows stay at least kSpsMinTile columns wide
-constexpr int kSpsMaxTile = 32;                                 // x columns per tile at most: 256-byte rows
-constexpr int kSpsMinTile = 8;                                  // and at least (64-byte rows): 64 KiB of LDS for lines above 512
 constexpr int kSpsBlocks = 2048;                                // blocks of the statistics and radix launches at most
 constexpr int kSpsPasses = 8, kSpsDigit = 256;                  // 8 passes of 8 bits
 // head of the workspace, in 8-byte words
@@ -39,103 +32,24 @@ constexpr int kSpsHeadWords = kSpsHist + kSpsPasses * 2 * kSpsDigit;
 constexpr size_t kSpsHeadBytes = (size_t)kSpsHeadWords * 8;     // cleared by the first launch
 constexpr size_t kSpsPartBytes = (size_t)2 * kSpsBlocks * 8;    // partial sums [A, B][block]: every used entry is written before it is read
 static_assert(kSpsHist == 64 && kSpsHeadBytes % 16 == 0 && kSpsPartBytes % 16 == 0, "the volumes behind the head stay 16-byte aligned");
-static_assert((size_t)RPNET_SURFACE_SPACING_MAX_DIM * kSpsMinTile * sizeof(double) <= 64 * 1024, "the longest line at the narrowest tile fits 64 KiB");
 static_assert(RPNET_SURFACE_SPACING_MAX_DIM == RPNET_SURFACE_MAX_DIM, "the extent limit of the integer path");
 
-struct SpsPair { const void* p[2]; int kind[2]; };
-
-__device__ __forceinline__ bool sps_fg(const void* __restrict__ p, const int kind, const size_t i, const int cls) {
-    switch (kind) {
-        case RPNET_SURFACE_U8: return (int)static_cast<const uint8_t*>(p)[i] == cls;
-        case RPNET_SURFACE_I32: return static_cast<const int32_t*>(p)[i] == cls;
-        case RPNET_SURFACE_I64: return static_cast<const int64_t*>(p)[i] == (int64_t)cls;
-        default: return static_cast<const float*>(p)[i] == (float)cls;
-    }
-}
+struct SpsMetric {                                              // w * o^2 along one axis: one rounding per product and per sum
+    typedef double T;
+    double w;                                                   // the weight of the axis of the pass
+    static constexpr T kNoSeed = DBL_MAX;                       // finite, above every reachable distance; DBL_MAX + w*o^2 never goes below it
+    static constexpr int kTileBytes = 32 * 1024;                // LDS of a y / z tile while its rows stay at least kMinTile columns wide
+    static constexpr int kMaxTile = 32, kMinTile = 8;           // 256-byte rows at most, 64-byte rows at least: 64 KiB of LDS for lines above 512
+    __device__ __forceinline__ T cost(const int o) const { return __dmul_rn(w, (double)(o * o)); }
+    static __device__ __forceinline__ T add(const T a, const T b) { return __dadd_rn(a, b); }
+    static __device__ __forceinline__ T lower(const T a, const T b) { return fmin(a, b); }
+};
+static_assert((size_t)RPNET_SURFACE_SPACING_MAX_DIM * SpsMetric::kMinTile * sizeof(double) <= 64 * 1024, "the longest line, narrowest tile: 64 KiB");
 
 // the memset of the head: counters, selection states and radix histograms to 0; grid ceil(kSpsHeadWords / 256)
 __global__ __launch_bounds__(256) void surface_spacing_clear_kernel(sps_u64* __restrict__ head) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < kSpsHeadWords) head[i] = 0ull;
-}
-
-// x pass with the border fused in: the border flags of surface_x_kernel.  A block owns R = 1024 / W whole lines (line = z * H + y);
-// grid (ceil(D*H / R), 2 volumes).
-__global__ __launch_bounds__(256) void surface_spacing_x_kernel(const SpsPair src, const int cls, const int D, const int H, const int W,
-                                                                const int R, const FastDiv div_w, const FastDiv div_h, const double wx,
-                                                                double* __restrict__ gA, double* __restrict__ gB) {
-    RPNET_PASS_PRIORITY();
-    __shared__ uint8_t fl[kSpsLineElems];       // bit 0: foreground; bit 1: the four y / z neighbours are foreground too
-    __shared__ uint8_t bd[kSpsLineElems];       // border flag
-    const int t = threadIdx.x, v = blockIdx.y;
-    const void* __restrict__ p = src.p[v];
-    const int kind = src.kind[v];
-    double* __restrict__ g = v ? gB : gA;
-    const int lines = D * H, line0 = blockIdx.x * R;
-    const int cnt = min(R, lines - line0) * W;      // <= 1024
-    const size_t HW = (size_t)H * W;
-
-    for (int i = t; i < cnt; i += 256) {
-        unsigned l, z;
-        const int x = (int)div_w.divmod((unsigned)i, l);
-        const int y = (int)div_h.divmod((unsigned)line0 + l, z);
-        const size_t off = (size_t)(line0 + (int)l) * W + x;
-        const bool f = sps_fg(p, kind, off, cls);
-        const bool inner = f && y > 0 && y < H - 1 && z > 0 && (int)z < D - 1 && sps_fg(p, kind, off - W, cls) &&
-                           sps_fg(p, kind, off + W, cls) && sps_fg(p, kind, off - HW, cls) && sps_fg(p, kind, off + HW, cls);
-        fl[i] = (uint8_t)((f ? 1 : 0) | (inner ? 2 : 0));
-    }
-    __syncthreads();
-    for (int i = t; i < cnt; i += 256) {
-        const int x = (int)div_w.mod((unsigned)i);
-        const unsigned c = fl[i];
-        const bool eroded = (c & 2u) && x > 0 && x < W - 1 && (fl[i - 1] & 1u) && (fl[i + 1] & 1u);
-        bd[i] = (uint8_t)((c & 1u) && !eroded);
-    }
-    __syncthreads();
-    for (int i = t; i < cnt; i += 256) {
-        const int x = (int)div_w.mod((unsigned)i);
-        double best = kSpsNoSeed;
-        for (int o = 0; o < W; ++o) {               // the first hit going outward is the nearest
-            if ((x >= o && bd[i - o]) || (x + o < W && bd[i + o])) {
-                best = __dmul_rn(wx, (double)(o * o));
-                break;
-            }
-        }
-        g[(size_t)line0 * W + i] = best;
-    }
-}
-
-// y / z pass, in place: surface_line_kernel in fp64.  A line has L voxels `lstride` apart; a block owns the lines of TX = 1 << txl
-// neighbouring x columns of one outer index (y pass: outer = z, z pass: outer = y); grid (ceil(W / TX), n_outer, 2 volumes); LDS:
-// L * TX doubles, all of it dynamic.
-__global__ __launch_bounds__(256) void surface_spacing_line_kernel(double* __restrict__ gA, double* __restrict__ gB, const int L,
-                                                                   const size_t lstride, const size_t ostride, const int W, const int txl,
-                                                                   const double w) {
-    RPNET_PASS_PRIORITY();
-    extern __shared__ double sps_tile[];
-    double* __restrict__ s = sps_tile;
-    const int t = threadIdx.x, TX = 1 << txl, x0 = blockIdx.x << txl;
-    const int nx = min(TX, W - x0), cnt = L << txl;                 // cnt * 8 <= 64 KiB
-    double* __restrict__ g = (blockIdx.z ? gB : gA) + (size_t)blockIdx.y * ostride + x0;
-
-    for (int i = t; i < cnt; i += 256) {
-        const int xl = i & (TX - 1), j = i >> txl;
-        s[i] = xl < nx ? g[(size_t)j * lstride + xl] : kSpsNoSeed;
-    }
-    __syncthreads();
-    for (int i = t; i < cnt; i += 256) {
-        const int xl = i & (TX - 1), j = i >> txl;
-        if (xl >= nx) continue;
-        double best = s[i];
-        for (int o = 1; o < L; ++o) {
-            const double wo2 = __dmul_rn(w, (double)(o * o));
-            if (wo2 >= best) break;                 // in[j] >= 0 and rounding is monotone: every further candidate is at least wo2
-            if (j >= o) best = fmin(best, __dadd_rn(s[i - (o << txl)], wo2));
-            if (j + o < L) best = fmin(best, __dadd_rn(s[i + (o << txl)], wo2));
-        }
-        g[(size_t)j * lstride + xl] = best;         // <= kSpsNoSeed: it started there or below
-    }
 }
 
 // n_A, n_B, the NSD counts, the largest squared distance and the partial sums of square roots.  A voxel is on a border exactly where
@@ -328,16 +242,6 @@ __global__ __launch_bounds__(256) void surface_spacing_finalize_kernel(const sps
     }
 }
 
-// columns of a y / z tile for lines of L voxels: the widest power of two up to kSpsMaxTile that keeps the tile within kSpsTileBytes, but
-// not below kSpsMinTile (the tile then grows to at most 64 KiB), and no wider than W needs
-static inline int sps_tile_log2(const int L, const int W) {
-    int txl = 0;
-    while ((2 << txl) <= kSpsMaxTile && (1 << txl) < W &&
-           ((size_t)L * (2 << txl) * sizeof(double) <= (size_t)kSpsTileBytes || (2 << txl) <= kSpsMinTile))
-        ++txl;
-    return txl;
-}
-
 }  // namespace rpnet
 
 extern "C" int rpnet_surface_spacing_abi_version(void) { return RPNET_SURFACE_SPACING_ABI_VERSION; }
@@ -355,27 +259,14 @@ extern "C" int rpnet_surface_spacing_tally(const void* pred, int pred_kind, cons
                                            const double* w, double tau2, int64_t* itable, int64_t irow, double* ftable, int64_t frow,
                                            int64_t n_rows, void* workspace, size_t workspace_bytes, rpnet_stream_t stream) {
     using namespace rpnet;
-    RPNET_REQUIRE(pred && truth && w && itable && ftable && workspace, RPNET_ERR_ARG, "surface_spacing_tally: null pointer");
-    RPNET_REQUIRE(pred_kind >= RPNET_SURFACE_U8 && pred_kind <= RPNET_SURFACE_F32 && truth_kind >= RPNET_SURFACE_U8 &&
-                      truth_kind <= RPNET_SURFACE_F32,
-                  RPNET_ERR_ARG, "surface_spacing_tally: element kinds %d, %d (0 uint8, 1 int32, 2 int64, 3 float32)", pred_kind, truth_kind);
-    RPNET_REQUIRE(D >= 1 && H >= 1 && W >= 1 && D <= RPNET_SURFACE_SPACING_MAX_DIM && H <= RPNET_SURFACE_SPACING_MAX_DIM &&
-                      W <= RPNET_SURFACE_SPACING_MAX_DIM,
-                  RPNET_ERR_SHAPE, "surface_spacing_tally: D=%d H=%d W=%d (every extent 1..%d)", D, H, W, RPNET_SURFACE_SPACING_MAX_DIM);
-    RPNET_REQUIRE(n_rows >= 1 && irow >= 0 && irow < n_rows && frow >= 0 && frow < n_rows, RPNET_ERR_ARG,
-                  "surface_spacing_tally: rows %lld and %lld of tables of %lld rows", (long long)irow, (long long)frow, (long long)n_rows);
+    RPNET_REQUIRE(w, RPNET_ERR_ARG, "surface_spacing_tally: null pointer");
+    if (const int rc = surface_check_tally("surface_spacing_tally", pred, pred_kind, truth, truth_kind, D, H, W, itable, irow, ftable, frow,
+                                           n_rows, workspace, workspace_bytes, rpnet_surface_spacing_workspace_bytes))
+        return rc;
     for (int a = 0; a < 3; ++a)
         RPNET_REQUIRE(std::isfinite(w[a]) && w[a] > 0.0, RPNET_ERR_ARG, "surface_spacing_tally: weight %d is %g (every weight finite and > 0)", a,
                       w[a]);
     RPNET_REQUIRE(!std::isnan(tau2), RPNET_ERR_ARG, "surface_spacing_tally: tau2 is NaN (a squared tolerance, or a negative value for none)");
-    const size_t need = rpnet_surface_spacing_workspace_bytes(D, H, W);
-    RPNET_REQUIRE(workspace_bytes >= need, RPNET_ERR_WORKSPACE, "surface_spacing_tally: workspace of %zu bytes, %zu needed", workspace_bytes,
-                  need);
-    static const size_t kAlign[4] = {1, 4, 8, 4};
-    RPNET_REQUIRE(((uintptr_t)pred % kAlign[pred_kind]) == 0 && ((uintptr_t)truth % kAlign[truth_kind]) == 0 && ((uintptr_t)itable % 8) == 0 &&
-                      ((uintptr_t)ftable % 8) == 0 && ((uintptr_t)workspace % 16) == 0,
-                  RPNET_ERR_ARG,
-                  "surface_spacing_tally: volumes must be aligned to their element, the tables to 8 and the workspace to 16 bytes");
 
     const hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)D * H * W;
@@ -386,23 +277,9 @@ extern "C" int rpnet_surface_spacing_tally(const void* pred, int pred_kind, cons
 
     hipLaunchKernelGGL(surface_spacing_clear_kernel, dim3(cdiv(kSpsHeadWords, 256)), dim3(256), 0, st, head);
 
-    SpsPair src{};
+    SurfPair src{};
     src.p[0] = pred, src.p[1] = truth, src.kind[0] = pred_kind, src.kind[1] = truth_kind;
-    const int R = kSpsLineElems / W, lines = D * H;
-    hipLaunchKernelGGL(surface_spacing_x_kernel, dim3(cdiv(lines, R), 2), dim3(256), 0, st, src, cls, D, H, W, R, FastDiv((unsigned)W),
-                       FastDiv((unsigned)H), w[2], gA, gB);
-
-    // y pass: lines along H (stride W) per z, weight w[1]; z pass: lines along D (stride H*W) per y, weight w[0]
-    const int len[2] = {H, D}, outer[2] = {D, H};
-    const size_t lstride[2] = {(size_t)W, (size_t)H * W}, ostride[2] = {(size_t)H * W, (size_t)W};
-    const double wl[2] = {w[1], w[0]};
-    for (int a = 0; a < 2; ++a) {
-        if (len[a] == 1) continue;                  // out[0] = in[0]
-        const int txl = sps_tile_log2(len[a], W);
-        const size_t lds = (size_t)len[a] * sizeof(double) << txl;      // <= 64 KiB: what a launch gets without asking
-        hipLaunchKernelGGL(surface_spacing_line_kernel, dim3(cdiv(W, 1 << txl), outer[a], 2), dim3(256), lds, st, gA, gB, len[a], lstride[a],
-                           ostride[a], W, txl, wl[a]);
-    }
+    surface_launch_passes(src, cls, D, H, W, SpsMetric{w[2]}, SpsMetric{w[1]}, SpsMetric{w[0]}, gA, gB, st);      // x, y, z: the tensor is [D, H, W]
 
     const int blocks = (int)std::min<size_t>((n + 255) / 256, (size_t)kSpsBlocks);
     const int iters = (int)((n + (size_t)blocks * 256 - 1) / ((size_t)blocks * 256));

@@ -136,7 +136,7 @@ _SIGS = {
 ABI_SYMBOLS = tuple(_SIGS)
 ABI_VERSION = 111     # RPNET_ABI_VERSION of include/rpnet_abi.h
 
-# the evaluation-item entry points: include/rpnet_eval_abi.h (additions beside rpnet_abi.h; their ledger is tests/eval_abi_ledger.py)
+# the evaluation-item entry points: include/rpnet_eval_abi.h (ledger: tests/eval_abi_ledger.py)
 _EVAL_SIGS = {
     "rpnet_eval_abi_version": (ci, []),
     "rpnet_eval_item_gather": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
@@ -146,7 +146,7 @@ _EVAL_SIGS = {
 EVAL_ABI_SYMBOLS = tuple(_EVAL_SIGS)
 EVAL_ABI_VERSION = 1     # RPNET_EVAL_ABI_VERSION of include/rpnet_eval_abi.h
 
-# the optimizer entry points: include/rpnet_optim_abi.h (additions beside the two headers above; their ledger is tests/optim_abi_ledger.py)
+# the optimizer entry points: include/rpnet_optim_abi.h (ledger: tests/optim_abi_ledger.py)
 i64p = C.POINTER(C.c_int64)
 _OPTIM_SIGS = {
     "rpnet_optim_abi_version": (ci, []),
@@ -157,8 +157,7 @@ _OPTIM_SIGS = {
 OPTIM_ABI_SYMBOLS = tuple(_OPTIM_SIGS)
 OPTIM_ABI_VERSION = 1     # RPNET_OPTIM_ABI_VERSION of include/rpnet_optim_abi.h
 
-# the gradient guard of the optimizer step: include/rpnet_guard_abi.h (additions beside the three headers above; their ledger is
-# tests/guard_abi_ledger.py)
+# the gradient guard of the optimizer step: include/rpnet_guard_abi.h (ledger: tests/guard_abi_ledger.py)
 _GUARD_SIGS = {
     "rpnet_guard_abi_version": (ci, []),
     "rpnet_grad_guard_init": (ci, [vp, cd, ci, C.c_int64]),
@@ -168,8 +167,7 @@ _GUARD_SIGS = {
 GUARD_ABI_SYMBOLS = tuple(_GUARD_SIGS)
 GUARD_ABI_VERSION = 1     # RPNET_GUARD_ABI_VERSION of include/rpnet_guard_abi.h
 
-# the surface-distance tallies of an evaluated volume: include/rpnet_surface_abi.h (additions beside the four headers above; their
-# ledger is tests/surface_abi_ledger.py)
+# the surface-distance tallies of an evaluated volume: include/rpnet_surface_abi.h (ledger: tests/surface_abi_ledger.py)
 _SURFACE_SIGS = {
     "rpnet_surface_abi_version": (ci, []),
     "rpnet_surface_workspace_bytes": (cs, [ci, ci, ci]),
@@ -178,8 +176,8 @@ _SURFACE_SIGS = {
 SURFACE_ABI_SYMBOLS = tuple(_SURFACE_SIGS)
 SURFACE_ABI_VERSION = 1     # RPNET_SURFACE_ABI_VERSION of include/rpnet_surface_abi.h
 
-# connected components of an evaluated volume and the largest-component filter: include/rpnet_cc_abi.h (additions beside the five
-# headers above; their ledger is tests/cc_abi_ledger.py)
+# connected components of an evaluated volume and the largest-component filter: include/rpnet_cc_abi.h
+# (ledger: tests/cc_abi_ledger.py)
 _CC_SIGS = {
     "rpnet_cc_abi_version": (ci, []),
     "rpnet_cc_workspace_bytes": (cs, [ci, ci, ci]),
@@ -189,8 +187,7 @@ _CC_SIGS = {
 CC_ABI_SYMBOLS = tuple(_CC_SIGS)
 CC_ABI_VERSION = 1     # RPNET_CC_ABI_VERSION of include/rpnet_cc_abi.h
 
-# surface distances on a grid with a per-axis voxel spacing: include/rpnet_surface_spacing_abi.h (additions beside the six headers above;
-# their ledger is tests/surface_spacing_abi_ledger.py)
+# surface distances on a grid with a per-axis voxel spacing: include/rpnet_surface_spacing_abi.h (ledger: tests/surface_spacing_abi_ledger.py)
 _SURFACE_SPACING_SIGS = {
     "rpnet_surface_spacing_abi_version": (ci, []),
     "rpnet_surface_spacing_workspace_bytes": (cs, [ci, ci, ci]),
@@ -199,8 +196,8 @@ _SURFACE_SPACING_SIGS = {
 SURFACE_SPACING_ABI_SYMBOLS = tuple(_SURFACE_SPACING_SIGS)
 SURFACE_SPACING_ABI_VERSION = 1     # RPNET_SURFACE_SPACING_ABI_VERSION of include/rpnet_surface_spacing_abi.h
 
-# hole filling and the small-component filter of an evaluated volume: include/rpnet_ccpost_abi.h (additions beside the seven headers
-# above; their ledger is tests/ccpost_abi_ledger.py)
+# hole filling and the small-component filter of an evaluated volume: include/rpnet_ccpost_abi.h
+# (ledger: tests/ccpost_abi_ledger.py)
 _CCPOST_SIGS = {
     "rpnet_ccpost_abi_version": (ci, []),
     "rpnet_ccpost_workspace_bytes": (cs, [ci, ci, ci]),
@@ -209,6 +206,19 @@ _CCPOST_SIGS = {
 }
 CCPOST_ABI_SYMBOLS = tuple(_CCPOST_SIGS)
 CCPOST_ABI_VERSION = 1     # RPNET_CCPOST_ABI_VERSION of include/rpnet_ccpost_abi.h
+
+
+# The families of entry points beside rpnet_abi.h, one per header: (header under include/, the words its version error uses, version
+# symbol, version this binding was written for, signatures).  load() binds and checks them all in one loop.
+SIDE_ABIS = [
+    ("rpnet_eval_abi.h", "evaluation-item", "rpnet_eval_abi_version", EVAL_ABI_VERSION, _EVAL_SIGS),
+    ("rpnet_optim_abi.h", "optimizer", "rpnet_optim_abi_version", OPTIM_ABI_VERSION, _OPTIM_SIGS),
+    ("rpnet_guard_abi.h", "gradient-guard", "rpnet_guard_abi_version", GUARD_ABI_VERSION, _GUARD_SIGS),
+    ("rpnet_surface_abi.h", "surface-distance", "rpnet_surface_abi_version", SURFACE_ABI_VERSION, _SURFACE_SIGS),
+    ("rpnet_cc_abi.h", "connected-component", "rpnet_cc_abi_version", CC_ABI_VERSION, _CC_SIGS),
+    ("rpnet_surface_spacing_abi.h", "surface-spacing", "rpnet_surface_spacing_abi_version", SURFACE_SPACING_ABI_VERSION, _SURFACE_SPACING_SIGS),
+    ("rpnet_ccpost_abi.h", "post-processing", "rpnet_ccpost_abi_version", CCPOST_ABI_VERSION, _CCPOST_SIGS),
+]
 
 
 def lib_path():
@@ -227,35 +237,16 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        for name, (res, args) in (list(_SIGS.items()) + list(_EVAL_SIGS.items()) + list(_OPTIM_SIGS.items()) + list(_GUARD_SIGS.items())
-                                  + list(_SURFACE_SIGS.items()) + list(_CC_SIGS.items()) + list(_SURFACE_SPACING_SIGS.items())
-                                  + list(_CCPOST_SIGS.items())):
-            fn = getattr(lib, name, None)
-            if fn is None:
-                raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
-            fn.restype, fn.argtypes = res, args
-        if lib.rpnet_eval_abi_version() != EVAL_ABI_VERSION:
-            raise RuntimeError(f"{_LIB_PATH} has evaluation-item ABI version {lib.rpnet_eval_abi_version()}, this binding was written for "
-                               f"{EVAL_ABI_VERSION} (include/rpnet_eval_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
-        if lib.rpnet_optim_abi_version() != OPTIM_ABI_VERSION:
-            raise RuntimeError(f"{_LIB_PATH} has optimizer ABI version {lib.rpnet_optim_abi_version()}, this binding was written for "
-                               f"{OPTIM_ABI_VERSION} (include/rpnet_optim_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
-        if lib.rpnet_guard_abi_version() != GUARD_ABI_VERSION:
-            raise RuntimeError(f"{_LIB_PATH} has gradient-guard ABI version {lib.rpnet_guard_abi_version()}, this binding was written for "
-                               f"{GUARD_ABI_VERSION} (include/rpnet_guard_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
-        if lib.rpnet_surface_abi_version() != SURFACE_ABI_VERSION:
-            raise RuntimeError(f"{_LIB_PATH} has surface-distance ABI version {lib.rpnet_surface_abi_version()}, this binding was written "
-                               f"for {SURFACE_ABI_VERSION} (include/rpnet_surface_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
-        if lib.rpnet_cc_abi_version() != CC_ABI_VERSION:
-            raise RuntimeError(f"{_LIB_PATH} has connected-component ABI version {lib.rpnet_cc_abi_version()}, this binding was written "
-                               f"for {CC_ABI_VERSION} (include/rpnet_cc_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
-        if lib.rpnet_surface_spacing_abi_version() != SURFACE_SPACING_ABI_VERSION:
-            raise RuntimeError(f"{_LIB_PATH} has surface-spacing ABI version {lib.rpnet_surface_spacing_abi_version()}, this binding was "
-                               f"written for {SURFACE_SPACING_ABI_VERSION} (include/rpnet_surface_spacing_abi.h): rebuild it with "
-                               "`make -C rpnet_amd/csrc`")
-        if lib.rpnet_ccpost_abi_version() != CCPOST_ABI_VERSION:
-            raise RuntimeError(f"{_LIB_PATH} has post-processing ABI version {lib.rpnet_ccpost_abi_version()}, this binding was written "
-                               f"for {CCPOST_ABI_VERSION} (include/rpnet_ccpost_abi.h): rebuild it with `make -C rpnet_amd/csrc`")
+        for sigs in [_SIGS] + [family[4] for family in SIDE_ABIS]:
+            for name, (res, args) in sigs.items():
+                fn = getattr(lib, name, None)
+                if fn is None:
+                    raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
+                fn.restype, fn.argtypes = res, args
+        for header, words, version_symbol, version, _ in SIDE_ABIS:
+            if getattr(lib, version_symbol)() != version:
+                raise RuntimeError(f"{_LIB_PATH} has {words} ABI version {getattr(lib, version_symbol)()}, this binding was written for "
+                                   f"{version} (include/{header}): rebuild it with `make -C rpnet_amd/csrc`")
         _lib = lib
     return _lib
 

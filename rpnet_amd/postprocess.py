@@ -26,11 +26,11 @@ import numpy as np
 import torch
 
 from . import hip
-from .surface import KINDS
+from ._volume_checks import KINDS, WorkspaceCache, prepare_class_filter
 
 STATS_ROW, COUNTS_ROW = 4, 3        # RPNET_CCPOST_STATS_ROW, RPNET_CCPOST_COUNTS_ROW
 OVERRUN_OFFSET = 24                 # RPNET_CCPOST_OVERRUN_OFFSET
-_post_workspaces = {}               # (device, (D, H, W)) -> uint8 tensor: a call allocates nothing once its shape has been seen
+_post_workspaces = WorkspaceCache(by_shape=True)    # post_overrun() reads the word a call left in the buffer of its shape
 
 
 def holes_mode_of(fill_holes):
@@ -73,63 +73,11 @@ def min_voxels_from_mm3(volume_mm3, spacing):
     return max(1, int(math.ceil(v / (sz * sy * sx))))
 
 
-def _post_workspace(device, shape):
-    key = (device, tuple(int(s) for s in shape))
-    ws = _post_workspaces.get(key)
-    if ws is None:
-        nbytes = hip.query("rpnet_ccpost_workspace_bytes", *key[1])
-        if nbytes == 0:
-            raise RuntimeError(f"rpnet_ccpost_workspace_bytes failed: {hip.load().rpnet_last_error_string().decode()}")
-        ws = _post_workspaces[key] = torch.empty((nbytes,), device=device, dtype=torch.uint8)
-    return ws
-
-
 def post_overrun(device, shape):
     """the `overrun` word the last call on a volume of this shape left in its workspace (0 unless a bounded loop ran out of its bound);
     a device-to-host copy: for tests and diagnosis, the product path reads the same fact from the statistics row (first column -1)"""
-    ws = _post_workspace(torch.device(device), shape)
+    ws, _ = _post_workspaces.get("rpnet_ccpost_workspace_bytes", torch.device(device), shape)
     return int(ws[OVERRUN_OFFSET:OVERRUN_OFFSET + 4].view(torch.int32).item())
-
-
-def _post_volume(t, what, fn):
-    if t.dtype not in KINDS:
-        raise ValueError(f"{fn}: {what} is {t.dtype}; uint8, int32, int64 and float32 volumes are accepted")
-    if t.dim() != 3 or not t.is_contiguous():
-        raise ValueError(f"{fn}: {what} must be a contiguous [D,H,W] tensor, got {tuple(t.shape)}")
-
-
-def _post_table(t, rows, cols, what, fn):
-    if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 2 or tuple(t.shape) != (rows, cols) or not t.is_contiguous():
-        raise ValueError(f"{fn}: {what} must be a contiguous int64 [{rows}, {cols}] tensor")
-
-
-def _post_prepare(fn, mask, classes, truth, out, counts, stats):
-    """the argument checks and the tables the two filters share -> (classes, out, counts, stats)"""
-    hip.require_gpu(mask, truth, out, counts, stats)
-    _post_volume(mask, "mask", fn)
-    classes = [int(c) for c in classes]
-    if not classes:
-        raise ValueError(f"{fn}: no class to process")
-    if truth is not None:
-        _post_volume(truth, "truth", fn)
-        if truth.shape != mask.shape:
-            raise ValueError(f"{fn}: mask {tuple(mask.shape)} and truth {tuple(truth.shape)} differ in shape")
-    elif counts is not None:
-        raise ValueError(f"{fn}: counts need a truth volume (there is nothing to tally without the ground truth)")
-    if out is None:
-        out = torch.empty(mask.shape, device=mask.device, dtype=torch.uint8)
-    elif out.dtype != torch.uint8 or out.shape != mask.shape or not out.is_contiguous():
-        raise ValueError(f"{fn}: out must be a contiguous uint8 tensor of shape {tuple(mask.shape)}")
-    if stats is None:
-        stats = torch.zeros((len(classes), STATS_ROW), device=mask.device, dtype=torch.int64)
-    _post_table(stats, len(classes), STATS_ROW, "stats", fn)
-    if truth is not None:
-        if counts is None:
-            counts = torch.zeros((len(classes), COUNTS_ROW), device=mask.device, dtype=torch.int64)
-        _post_table(counts, len(classes), COUNTS_ROW, "counts", fn)
-    if len({t.device for t in (mask, truth, out, counts, stats) if t is not None}) != 1:
-        raise ValueError(f"{fn}: the volumes and the tables must be on one device")
-    return classes, out, counts, stats
 
 
 def fill_holes(mask, classes, connectivity=6, per_slice=False, max_hole=None, truth=None, out=None, counts=None, stats=None):
@@ -139,7 +87,7 @@ def fill_holes(mask, classes, connectivity=6, per_slice=False, max_hole=None, tr
     bound.  Voxels of value 0 inside a hole of a listed class become that class; every other value passes through (as uint8).  out may be
     `mask` itself when that is uint8 (in place).  truth: the Dice counts of each class in the result are ADDED to counts (made of zeros
     when not handed in).  Launches only: nothing is copied or synchronised."""
-    classes, out, counts, stats = _post_prepare("fill_holes", mask, classes, truth, out, counts, stats)
+    classes, out, counts, stats = prepare_class_filter("fill_holes", "process", mask, classes, truth, out, counts, stats, STATS_ROW, COUNTS_ROW)
     if max_hole is None:
         bound = 0
     else:
@@ -148,7 +96,7 @@ def fill_holes(mask, classes, connectivity=6, per_slice=False, max_hole=None, tr
             raise ValueError(f"fill_holes: max_hole must be None (no bound) or at least 1 voxel, got {max_hole!r}")
     conn = hole_connectivity_of(connectivity, bool(per_slice))
     D, H, W = mask.shape
-    ws = _post_workspace(mask.device, (D, H, W))
+    ws, _ = _post_workspaces.get("rpnet_ccpost_workspace_bytes", mask.device, (D, H, W))
     src = mask
     for r, c in enumerate(classes):
         hip.call("rpnet_ccpost_fill_holes", hip.ptr(src), KINDS[src.dtype], hip.ptr(out), c, D, H, W, conn, int(bool(per_slice)), bound,
@@ -162,9 +110,9 @@ def remove_small(mask, classes, min_voxels, connectivity=6, truth=None, out=None
     """Remove the components of fewer than `min_voxels` voxels of every class in `classes`, one `rpnet_ccpost_remove_small` call per class
     on the current stream -> (out, counts, stats) as fill_holes gives them.  connectivity: 6 or 26.  Voxels of a removed component
     become 0; every other value passes through (as uint8)."""
-    classes, out, counts, stats = _post_prepare("remove_small", mask, classes, truth, out, counts, stats)
+    classes, out, counts, stats = prepare_class_filter("remove_small", "process", mask, classes, truth, out, counts, stats, STATS_ROW, COUNTS_ROW)
     D, H, W = mask.shape
-    ws = _post_workspace(mask.device, (D, H, W))
+    ws, _ = _post_workspaces.get("rpnet_ccpost_workspace_bytes", mask.device, (D, H, W))
     src = mask
     for r, c in enumerate(classes):
         hip.call("rpnet_ccpost_remove_small", hip.ptr(src), KINDS[src.dtype], hip.ptr(out), c, D, H, W, int(connectivity), int(min_voxels),

@@ -19,28 +19,19 @@ import numpy as np
 import torch
 
 from . import hip
+from ._volume_checks import KINDS, WorkspaceCache, check_table, check_volume, fmt, hd95_from, mean_of, one_device  # noqa: F401  (KINDS, fmt: public)
 
 IROW, FROW = 6, 2           # RPNET_SURFACE_IROW, RPNET_SURFACE_FROW
 MAX_DIM = 1024              # RPNET_SURFACE_MAX_DIM
 NO_SEED = 1 << 29           # the transform of a volume without a border voxel
-KINDS = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}      # RPNET_SURFACE_U8 / I32 / I64 / F32
 _NONE = {"hd95": None, "hd": None, "assd": None}
-_workspaces = {}            # device -> uint8 tensor, grown on demand: a tally allocates nothing once its shape has been seen
-
-
-def _workspace(device, nbytes):
-    ws = _workspaces.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = _workspaces[device] = torch.empty((nbytes,), device=device, dtype=torch.uint8)
-    return ws
+_workspaces = WorkspaceCache(by_shape=False)
 
 
 def check_surface_tables(itable, ftable, what="surface_tally"):
     """the two tables of surface rows: a contiguous int64 [n, 6] and a contiguous float64 [n, 2] tensor"""
-    if not torch.is_tensor(itable) or itable.dtype != torch.int64 or itable.dim() != 2 or itable.shape[1] != IROW or not itable.is_contiguous():
-        raise ValueError(f"{what}: the integer table must be a contiguous int64 [n, {IROW}] tensor")
-    if not torch.is_tensor(ftable) or ftable.dtype != torch.float64 or ftable.dim() != 2 or ftable.shape[1] != FROW or not ftable.is_contiguous():
-        raise ValueError(f"{what}: the sum table must be a contiguous float64 [n, {FROW}] tensor")
+    check_table(itable, None, IROW, torch.int64, "the integer table", what)
+    check_table(ftable, None, FROW, torch.float64, "the sum table", what)
     if itable.shape[0] != ftable.shape[0]:
         raise ValueError(f"{what}: the tables have {itable.shape[0]} and {ftable.shape[0]} rows")
 
@@ -51,29 +42,16 @@ def surface_tally(pred, truth, itable, irow, ftable, frow, cls=1):
     (each its own kind), every extent 1..1024; itable int64 [n,6], ftable float64 [n,2] on the same device.  Launches only: nothing is
     copied or synchronised."""
     hip.require_gpu(pred, truth, itable, ftable)
-    for t, what in ((pred, "pred"), (truth, "truth")):
-        if t.dtype not in KINDS:
-            raise ValueError(f"surface_tally: {what} is {t.dtype}; uint8, int32, int64 and float32 volumes are accepted")
-        if t.dim() != 3 or not t.is_contiguous():
-            raise ValueError(f"surface_tally: {what} must be a contiguous [D,H,W] tensor, got {tuple(t.shape)}")
+    check_volume(pred, "pred", "surface_tally")
+    check_volume(truth, "truth", "surface_tally")
     if pred.shape != truth.shape:
         raise ValueError(f"surface_tally: pred {tuple(pred.shape)} and truth {tuple(truth.shape)} differ in shape")
     check_surface_tables(itable, ftable)
-    if len({pred.device, truth.device, itable.device, ftable.device}) != 1:
-        raise ValueError("surface_tally: the volumes and the tables must be on one device")
+    one_device("surface_tally", pred, truth, itable, ftable)
     D, H, W = pred.shape
-    nbytes = hip.query("rpnet_surface_workspace_bytes", D, H, W)
-    if nbytes == 0:
-        raise RuntimeError(f"rpnet_surface_workspace_bytes failed: {hip.load().rpnet_last_error_string().decode()}")
-    ws = _workspace(pred.device, nbytes)
+    ws, nbytes = _workspaces.get("rpnet_surface_workspace_bytes", pred.device, (D, H, W))
     hip.call("rpnet_surface_tally", hip.ptr(pred), KINDS[pred.dtype], hip.ptr(truth), KINDS[truth.dtype], int(cls), D, H, W,
              hip.ptr(itable), int(irow), hip.ptr(ftable), int(frow), itable.shape[0], hip.ptr(ws), nbytes)
-
-
-def _lerp(a, b, t):
-    """numpy's interpolation between two order statistics (numpy/lib/_function_base_impl.py:_lerp)"""
-    d = b - a
-    return b - d * (1 - t) if t >= 0.5 else a + d * t
 
 
 def surface_from_rows(irow, frow, spacing=1.0):
@@ -86,9 +64,7 @@ def surface_from_rows(irow, frow, spacing=1.0):
     n_a, n_b, d2_k, d2_k1, d2_max, k = (int(v) for v in irow)
     if k < 0 or n_a == 0 or n_b == 0:
         return dict(_NONE)
-    n = n_a + n_b
-    gamma = (n - 1) * 0.95 - k                      # numpy: virtual index (n - 1) * q, q = 95 / 100
-    hd95 = _lerp(math.sqrt(d2_k), math.sqrt(d2_k1), gamma)
+    hd95 = hd95_from(d2_k, d2_k1, n_a + n_b, k)
     assd = (float(frow[0]) / n_a + float(frow[1]) / n_b) / 2
     s = float(spacing)
     return {"hd95": hd95 * s, "hd": math.sqrt(d2_max) * s, "assd": assd * s}
@@ -100,11 +76,6 @@ def surface_figures(itable, ftable, spacing=1.0):
     return [surface_from_rows(i, f, spacing) for i, f in zip(it, ft)]
 
 
-def fmt(v):
-    """a figure as the evaluation lines print it"""
-    return "None" if v is None else f"{v:.4f}"
-
-
 def line_suffix(fewshot, affine):
     """what an item line gains: ` hd95 <fewshot> (<affine>) assd <fewshot> (<affine>)`"""
     return f" hd95 {fmt(fewshot['hd95'])} ({fmt(affine['hd95'])}) assd {fmt(fewshot['assd'])} ({fmt(affine['assd'])})"
@@ -112,10 +83,7 @@ def line_suffix(fewshot, affine):
 
 def mean_suffix(fewshot, affine):
     """what a class line gains: the same four figures as means over the items where they are not None"""
-    def mean(rows, key):
-        vals = [r[key] for r in rows if r[key] is not None]
-        return float(np.mean(vals)) if vals else None
-    return line_suffix({k: mean(fewshot, k) for k in ("hd95", "assd")}, {k: mean(affine, k) for k in ("hd95", "assd")})
+    return line_suffix({k: mean_of(fewshot, k) for k in ("hd95", "assd")}, {k: mean_of(affine, k) for k in ("hd95", "assd")})
 
 
 # ------------------------------------------------------------------------------------------------- the numpy restatement

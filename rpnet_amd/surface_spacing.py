@@ -22,19 +22,13 @@ import numpy as np
 import torch
 
 from . import hip
-from .surface import KINDS, MAX_DIM, _lerp, border_reference, fmt
+from ._volume_checks import KINDS, WorkspaceCache, check_table, check_volume, fmt, hd95_from, mean_of, one_device
+from .surface import MAX_DIM, border_reference  # noqa: F401  MAX_DIM: the extent limit is that of the integer path
 
 IROW, FROW = 5, 5           # RPNET_SURFACE_SPACING_IROW, RPNET_SURFACE_SPACING_FROW
 NO_SEED = float(np.finfo(np.float64).max)       # the transform of a volume without a border voxel (DBL_MAX)
 _NONE = {"hd95": None, "hd": None, "assd": None, "nsd": None}
-_workspaces = {}            # device -> uint8 tensor, grown on demand: a tally allocates nothing once its shape has been seen
-
-
-def _spacing_workspace(device, nbytes):
-    ws = _workspaces.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = _workspaces[device] = torch.empty((nbytes,), device=device, dtype=torch.uint8)
-    return ws
+_workspaces = WorkspaceCache(by_shape=False)
 
 
 def check_spacing(spacing, what="surface_tally_spacing"):
@@ -62,10 +56,8 @@ def tolerance_squared(tau):
 
 def check_spacing_tables(itable, ftable, what="surface_tally_spacing"):
     """the two tables of spacing rows: a contiguous int64 [n, 5] and a contiguous float64 [n, 5] tensor"""
-    if not torch.is_tensor(itable) or itable.dtype != torch.int64 or itable.dim() != 2 or itable.shape[1] != IROW or not itable.is_contiguous():
-        raise ValueError(f"{what}: the integer table must be a contiguous int64 [n, {IROW}] tensor (the widths under a spacing)")
-    if not torch.is_tensor(ftable) or ftable.dtype != torch.float64 or ftable.dim() != 2 or ftable.shape[1] != FROW or not ftable.is_contiguous():
-        raise ValueError(f"{what}: the float table must be a contiguous float64 [n, {FROW}] tensor (the widths under a spacing)")
+    check_table(itable, None, IROW, torch.int64, "the integer table", what, " (the widths under a spacing)")
+    check_table(ftable, None, FROW, torch.float64, "the float table", what, " (the widths under a spacing)")
     if itable.shape[0] != ftable.shape[0]:
         raise ValueError(f"{what}: the tables have {itable.shape[0]} and {ftable.shape[0]} rows")
 
@@ -76,24 +68,17 @@ def surface_tally_spacing(pred, truth, spacing, itable, irow, ftable, frow, cls=
     ftable float64 [n,5] on the same device; tau: the NSD tolerance in the unit of the spacing, None for none.  Launches only: nothing is
     copied or synchronised."""
     hip.require_gpu(pred, truth, itable, ftable)
-    for t, what in ((pred, "pred"), (truth, "truth")):
-        if t.dtype not in KINDS:
-            raise ValueError(f"surface_tally_spacing: {what} is {t.dtype}; uint8, int32, int64 and float32 volumes are accepted")
-        if t.dim() != 3 or not t.is_contiguous():
-            raise ValueError(f"surface_tally_spacing: {what} must be a contiguous [D,H,W] tensor, got {tuple(t.shape)}")
+    check_volume(pred, "pred", "surface_tally_spacing")
+    check_volume(truth, "truth", "surface_tally_spacing")
     if pred.shape != truth.shape:
         raise ValueError(f"surface_tally_spacing: pred {tuple(pred.shape)} and truth {tuple(truth.shape)} differ in shape")
     check_spacing_tables(itable, ftable)
-    if len({pred.device, truth.device, itable.device, ftable.device}) != 1:
-        raise ValueError("surface_tally_spacing: the volumes and the tables must be on one device")
+    one_device("surface_tally_spacing", pred, truth, itable, ftable)
     w = (ctypes.c_double * 3)(*spacing_weights(spacing))
     if tau is not None and math.isnan(tau):
         raise ValueError("surface_tally_spacing: tau is NaN")
     D, H, W = pred.shape
-    nbytes = hip.query("rpnet_surface_spacing_workspace_bytes", D, H, W)
-    if nbytes == 0:
-        raise RuntimeError(f"rpnet_surface_spacing_workspace_bytes failed: {hip.load().rpnet_last_error_string().decode()}")
-    ws = _spacing_workspace(pred.device, nbytes)
+    ws, nbytes = _workspaces.get("rpnet_surface_spacing_workspace_bytes", pred.device, (D, H, W))
     hip.call("rpnet_surface_spacing_tally", hip.ptr(pred), KINDS[pred.dtype], hip.ptr(truth), KINDS[truth.dtype], int(cls), D, H, W, w,
              tolerance_squared(tau), hip.ptr(itable), int(irow), hip.ptr(ftable), int(frow), itable.shape[0], hip.ptr(ws), nbytes)
 
@@ -107,8 +92,7 @@ def figures_from_rows(irow, frow, tau=None):
         return dict(_NONE)
     d2_k, d2_k1, d2_max, sum_a, sum_b = (float(v) for v in frow)
     n = n_a + n_b
-    gamma = (n - 1) * 0.95 - k                      # numpy: virtual index (n - 1) * q, q = 95 / 100
-    hd95 = _lerp(math.sqrt(d2_k), math.sqrt(d2_k1), gamma)
+    hd95 = hd95_from(d2_k, d2_k1, n, k)
     nsd = (within_a + within_b) / n if tolerance_squared(tau) >= 0 else None
     return {"hd95": hd95, "hd": math.sqrt(d2_max), "assd": (sum_a / n_a + sum_b / n_b) / 2, "nsd": nsd}
 
@@ -130,11 +114,8 @@ def line_suffix_mm(fewshot, affine, nsd):
 
 def mean_suffix_mm(fewshot, affine, nsd):
     """what a class line gains: the same figures as means over the items where they are not None"""
-    def mean(rows, key):
-        vals = [r[key] for r in rows if r[key] is not None]
-        return float(np.mean(vals)) if vals else None
     keys = ("hd95", "assd", "nsd")
-    return line_suffix_mm({k: mean(fewshot, k) for k in keys}, {k: mean(affine, k) for k in keys}, nsd)
+    return line_suffix_mm({k: mean_of(fewshot, k) for k in keys}, {k: mean_of(affine, k) for k in keys}, nsd)
 
 
 # ------------------------------------------------------------------------------------------------- the numpy restatement
