@@ -21,6 +21,7 @@ import torch
 
 from . import augment as A
 from . import components as CC
+from . import morphology as MO
 from . import postprocess as PP
 from . import hip
 from . import registration as R
@@ -180,7 +181,8 @@ def item_spacings(source, n, spacing):
 
 
 def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False,
-                     spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None, min_component=None):
+                     spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None, min_component=None,
+                     opening=None, closing=None, morph_per_slice=False):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -209,15 +211,27 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     of fill_holes, 4..7 that of remove_small, zeros for a stage that is off), crosses with the others and arrives as out["post_stats"];
     the tables named under keep_largest then describe the end of the chain (out["components"] only with keep_largest); every item line
     gains ` holes <n> (<filled> voxels filled)` and ` small <n> (<removed> voxels removed)` for the stages that are on, after the lcc
-    figures, every class line their means; save_pred writes the end of the chain.  With these options off nothing changes."""
+    figures, every class line their means; save_pred writes the end of the chain.  With these options off nothing changes.
+    opening, closing (None, a radius in voxels, ('rho', n), or (x, 'mm') under a spacing, with "header" resolved per item; a spacing is
+    then accepted without surface=True), morph_per_slice: the ball morphology of VolumeSegmenter (rpnet_amd.morphology); the chain
+    becomes open -> remove small -> keep largest -> close -> fill holes.  One more device table, int64 [n_items, K-1, 8] (columns 0..3
+    the statistics row of the opening, 4..7 that of the closing, zeros for a stage that is off), is fetched once per data set and
+    arrives as out["morph_stats"]; every item line gains ` open -<removed> +<added>` and ` close -<removed> +<added>` for the stages
+    that are on, after the figures above, every class line their means.  With both None nothing changes."""
     from .utils import nrrd
     from .volume import check_min_component
     conn = CC.connectivity_of(keep_largest)
     holes_on, small_min = PP.holes_mode_of(fill_holes) is not None, check_min_component(min_component)
     small_on = small_min is not None
-    chain = bool(conn) or holes_on or small_on
-    mm3 = isinstance(small_min, tuple)
-    if mm3 and spacing is None:
+    open_r = None if opening is None else MO.check_radius(opening, "evaluate_dataset: opening")
+    close_r = None if closing is None else MO.check_radius(closing, "evaluate_dataset: closing")
+    morph_on = open_r is not None or close_r is not None
+    morph_mm = any(r is not None and r[0] == "mm" for r in (open_r, close_r))
+    if morph_mm and spacing is None:
+        raise ValueError("evaluate_dataset: an opening or closing radius in mm needs a spacing (a triple or 'header')")
+    chain = bool(conn) or holes_on or small_on or morph_on
+    mm3 = isinstance(small_min, tuple) or morph_mm
+    if isinstance(small_min, tuple) and spacing is None:
         raise ValueError("evaluate_dataset: min_component in mm3 needs a spacing (a triple or 'header')")
     classes = config["eval_classes"]
     n = len(source) if n_items is None else min(n_items, len(source))
@@ -229,7 +243,8 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     mm = spacing is not None
     WI, WF = (SS.IROW, SS.FROW) if mm else (SF.IROW, SF.FROW)
     seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False, surface_tolerance=surface_tolerance,
-                          fill_holes=fill_holes, hole_connectivity=hole_connectivity, max_hole=max_hole, min_component=min_component)
+                          fill_holes=fill_holes, hole_connectivity=hole_connectivity, max_hole=max_hole, min_component=min_component,
+                          **(dict(opening=opening, closing=closing, morph_per_slice=morph_per_slice) if morph_on else {}))
     dev = next(net.parameters()).device
     T, K = net.num_iter, 2
     table = torch.zeros((n, T + 2, K - 1, 3), device=dev, dtype=torch.int64)
@@ -241,6 +256,7 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     post_i = torch.zeros((n, K - 1, WI), device=dev, dtype=torch.int64) if chain and surface else None
     post_f = torch.zeros((n, K - 1, WF), device=dev, dtype=torch.float64) if chain and surface else None
     post_w = torch.zeros((n, K - 1, 2 * PP.STATS_ROW), device=dev, dtype=torch.int64) if holes_on or small_on else None
+    post_m = torch.zeros((n, K - 1, 2 * MO.STATS_ROW), device=dev, dtype=torch.int64) if morph_on else None
     meta, masks = [], []
     for j in range(n):
         s = source.item(j)
@@ -251,6 +267,8 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             extra["post_out"] = (post_c[j], post_s[j]) + (((post_i[j], post_f[j]),) if surface else ())
         if post_w is not None:
             extra["post_stats_out"] = post_w[j]
+        if post_m is not None:
+            extra["morph_stats_out"] = post_m[j]
         res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j],
                   **extra)
         ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
@@ -270,6 +288,7 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
                 out["surface_i"], out["surface_f"] = surf_i, surf_f
     lcc_dice, lcc_fig, lcc_surf = defaultdict(list), defaultdict(list), defaultdict(list)
     holes_fig, small_fig = defaultdict(list), defaultdict(list)
+    open_fig, close_fig = defaultdict(list), defaultdict(list)
     if chain:
         post_c, post_s = post_c.cpu().numpy(), post_s.cpu().numpy()
         if out is not None:
@@ -280,6 +299,10 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             post_w = post_w.cpu().numpy()
             if out is not None:
                 out["post_stats"] = post_w
+        if post_m is not None:
+            post_m = post_m.cpu().numpy()
+            if out is not None:
+                out["morph_stats"] = post_m
         if surface:
             post_i, post_f = post_i.cpu().numpy(), post_f.cpu().numpy()
             if out is not None:
@@ -317,6 +340,12 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             holes_fig[name].append(h)
             small_fig[name].append(sm)
             line += PP.line_suffix(h, sm)
+        if post_m is not None:
+            op = MO.morph_figures(post_m[j, :, :MO.STATS_ROW])[0] if open_r is not None else None
+            cl = MO.morph_figures(post_m[j, :, MO.STATS_ROW:])[0] if close_r is not None else None
+            open_fig[name].append(op)
+            close_fig[name].append(cl)
+            line += MO.line_suffix(op, cl)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
@@ -326,5 +355,7 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
                   + ((SS.mean_suffix_mm(surf_few[name], surf_aff[name], surface_tolerance is not None) if mm
                       else SF.mean_suffix(surf_few[name], surf_aff[name])) if surface else "")
                   + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else "")
-                  + (PP.mean_suffix(holes_fig[name] if holes_on else None, small_fig[name] if small_on else None) if post_w is not None else ""))
+                  + (PP.mean_suffix(holes_fig[name] if holes_on else None, small_fig[name] if small_on else None) if post_w is not None else "")
+                  + (MO.mean_suffix(open_fig[name] if open_r is not None else None, close_fig[name] if close_r is not None else None)
+                     if post_m is not None else ""))
     return dsc_affine, dsc_fewshot, dsc_ref

@@ -207,6 +207,17 @@ _CCPOST_SIGS = {
 CCPOST_ABI_SYMBOLS = tuple(_CCPOST_SIGS)
 CCPOST_ABI_VERSION = 1     # RPNET_CCPOST_ABI_VERSION of include/rpnet_ccpost_abi.h
 
+# ball morphology of an evaluated volume (erode, dilate, open, close): include/rpnet_morph_abi.h (ledger: tests/morph_abi_ledger.py)
+_MORPH_TAIL = [vp, ci, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, cs, vp]     # truth, kind, counts, row, stats, row, rows, workspace, bytes, stream
+_MORPH_SIGS = {
+    "rpnet_morph_abi_version": (ci, []),
+    "rpnet_morph_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_morph_apply": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, C.c_int64, ci, ci] + _MORPH_TAIL),
+    "rpnet_morph_apply_spacing": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, C.POINTER(cd), cd, ci, ci] + _MORPH_TAIL),
+}
+MORPH_ABI_SYMBOLS = tuple(_MORPH_SIGS)
+MORPH_ABI_VERSION = 1     # RPNET_MORPH_ABI_VERSION of include/rpnet_morph_abi.h
+
 
 # The families of entry points beside rpnet_abi.h, one per header: (header under include/, the words its version error uses, version
 # symbol, version this binding was written for, signatures).  load() binds and checks them all in one loop.
@@ -218,6 +229,7 @@ SIDE_ABIS = [
     ("rpnet_cc_abi.h", "connected-component", "rpnet_cc_abi_version", CC_ABI_VERSION, _CC_SIGS),
     ("rpnet_surface_spacing_abi.h", "surface-spacing", "rpnet_surface_spacing_abi_version", SURFACE_SPACING_ABI_VERSION, _SURFACE_SPACING_SIGS),
     ("rpnet_ccpost_abi.h", "post-processing", "rpnet_ccpost_abi_version", CCPOST_ABI_VERSION, _CCPOST_SIGS),
+    ("rpnet_morph_abi.h", "morphology", "rpnet_morph_abi_version", MORPH_ABI_VERSION, _MORPH_SIGS),
 ]
 
 

@@ -17,6 +17,7 @@ import torch
 
 from . import components as CC
 from . import hip
+from . import morphology as MO
 from . import postprocess as PP
 from . import surface as SF
 from . import surface_spacing as SS
@@ -207,10 +208,20 @@ class VolumeSegmenter:
                   post_out is accepted with any stage on and keeps its shape rules; its statistics table [K-1, 4] belongs to keep_largest and
                   is left as it is without that stage.
       post_stats_out  int64 [K-1, 8] on the net's device (needs post_out): columns 0..3 take the statistics row of fill_holes, 4..7 that
-                  of remove_small (the columns of a stage that is off are left as they are); 'holes' and 'small' of `post` are None."""
+                  of remove_small (the columns of a stage that is off are left as they are); 'holes' and 'small' of `post` are None.
+      opening, closing  None, a radius in voxels, ('rho', n) for a squared voxel radius, or (x, 'mm') under a spacing: every foreground
+                  class is opened / closed by the ball (rpnet_amd.morphology; outside the volume counts as object in the erosions).
+                  morph_per_slice: every z slice on its own.  The fixed order of the chain becomes
+                  open -> remove small -> keep largest -> close -> fill holes: opening detaches what keep_largest should drop, closing
+                  seals what fill_holes should fill.  `post` gains 'opening' and 'closing': per class the figures of
+                  morphology.morph_figures (None for a stage that is off).  With both None every launch and every output is what it
+                  is without them.
+      morph_stats_out  int64 [K-1, 8] on the net's device (needs post_out): columns 0..3 take the statistics row of the opening, 4..7
+                  that of the closing (the columns of a stage that is off are left as they are); 'opening' and 'closing' of `post`
+                  are None."""
 
     def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None, fill_holes=False,
-                 hole_connectivity=None, max_hole=None, min_component=None):
+                 hole_connectivity=None, max_hole=None, min_component=None, opening=None, closing=None, morph_per_slice=False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.spacing = None if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
@@ -227,6 +238,11 @@ class VolumeSegmenter:
             raise ValueError(f"VolumeSegmenter: max_hole must be None (no bound) or at least 1 voxel, got {max_hole!r}")
         self.max_hole = None if max_hole is None else int(max_hole)
         self.min_component = check_min_component(min_component)
+        self.opening = None if opening is None else MO.check_radius(opening, "VolumeSegmenter: opening")
+        self.closing = None if closing is None else MO.check_radius(closing, "VolumeSegmenter: closing")
+        self.morph_per_slice = bool(morph_per_slice)
+        if self.morph_per_slice and self.opening is None and self.closing is None:
+            raise ValueError("VolumeSegmenter: morph_per_slice needs opening or closing")
         self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
         if self._graphed_eval is not None and self._graphed_eval.net is not net:
             raise ValueError("VolumeSegmenter: the GraphedEval handed in wraps another net")
@@ -289,9 +305,9 @@ class VolumeSegmenter:
         figures = self._figures(itab, ftab, spacing)
         return {"fewshot": figures[:K - 1], "affine": figures[K - 1:]}
 
-    def _post(self, mask, labels, K, post_out, spacing=None, post_stats_out=None):
-        """the clean-up chain on the final mask (remove small -> keep largest -> fill holes, each stage that is on), and what is
-        measured at its end.  Only the last stage tallies the Dice counts: they describe the end of the chain."""
+    def _post(self, mask, labels, K, post_out, spacing=None, post_stats_out=None, morph_stats_out=None):
+        """the clean-up chain on the final mask (open -> remove small -> keep largest -> close -> fill holes, each stage that is on), and
+        what is measured at its end.  Only the last stage tallies the Dice counts: they describe the end of the chain."""
         dev = mask.device
         wi, wf = surface_widths(spacing)
         with_surface = self.surface and labels is not None
@@ -304,7 +320,8 @@ class VolumeSegmenter:
             surf = (torch.zeros((K - 1, wi), device=dev, dtype=torch.int64),
                     torch.zeros((K - 1, wf), device=dev, dtype=torch.float64)) if with_surface else None
         kept = torch.empty_like(mask)
-        stages = [name for name, on in (("small", self.min_component is not None), ("largest", bool(self.keep_largest)),
+        stages = [name for name, on in (("opening", self.opening is not None), ("small", self.min_component is not None),
+                                        ("largest", bool(self.keep_largest)), ("closing", self.closing is not None),
                                         ("holes", self.fill_holes is not None)) if on]
         tables, src = {}, mask
         for name in stages:
@@ -319,6 +336,11 @@ class VolumeSegmenter:
                 tables[name] = PP.remove_small(src, range(1, K), m, connectivity=self.keep_largest or 6, **tally)[2]
             elif name == "largest":
                 CC.keep_largest(src, classes=range(1, K), connectivity=self.keep_largest, stats=stats, **tally)
+            elif name in ("opening", "closing"):
+                radius = getattr(self, name)
+                fn = MO.opening if name == "opening" else MO.closing
+                tables[name] = fn(src, range(1, K), (radius[1], "mm") if radius[0] == "mm" else radius, spacing=spacing,
+                                  per_slice=self.morph_per_slice, **tally)[2]
             else:
                 tables[name] = PP.fill_holes(src, range(1, K), connectivity=self.hole_connectivity, per_slice=self.fill_holes,
                                              max_hole=self.max_hole, **tally)[2]
@@ -330,11 +352,21 @@ class VolumeSegmenter:
             for at, name in ((0, "holes"), (PP.STATS_ROW, "small")):
                 if name in tables:
                     post_stats_out[:, at:at + PP.STATS_ROW].copy_(tables[name])
+        if morph_stats_out is not None:
+            for at, name in ((0, "opening"), (MO.STATS_ROW, "closing")):
+                if name in tables:
+                    morph_stats_out[:, at:at + MO.STATS_ROW].copy_(tables[name])
         post = {"mask": kept, "counts": None, "dice": None, "components": None, "surface": None}
-        extended = stages != ["largest"]
+        morph = self.opening is not None or self.closing is not None
+        extended = any(name in ("small", "holes") for name in stages)
         if extended:
             post.update(holes=None, small=None)
+        if morph:
+            post.update(opening=None, closing=None)
         if post_out is None:
+            for name in ("opening", "closing"):
+                if name in tables:
+                    post[name] = MO.morph_figures(tables[name].cpu().numpy())
             if self.keep_largest:
                 post["components"] = CC.components_figures(stats.cpu().numpy())
             if "holes" in tables:
@@ -349,9 +381,10 @@ class VolumeSegmenter:
         return post
 
     def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None,
-                 post_out=None, spacing=None, post_stats_out=None):
+                 post_out=None, spacing=None, post_stats_out=None, morph_stats_out=None):
         dev = next(self.net.parameters()).device
-        chain = bool(self.keep_largest) or self.fill_holes is not None or self.min_component is not None
+        morph = self.opening is not None or self.closing is not None
+        chain = bool(self.keep_largest) or self.fill_holes is not None or self.min_component is not None or morph
         spacing = self.spacing if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
         if self.surface_tolerance is not None and spacing is None and self.surface:
             raise ValueError("VolumeSegmenter: surface_tolerance is a distance in the unit of a spacing; give spacing= as well")
@@ -390,6 +423,18 @@ class VolumeSegmenter:
                 raise ValueError(f"post_stats_out must be a contiguous int64 [{K - 1}, {2 * PP.STATS_ROW}] tensor")
             if post_stats_out.device != dev:
                 raise ValueError(f"post_stats_out is on {post_stats_out.device}, the net on {dev}")
+        if morph:
+            for radius in (self.opening, self.closing):
+                if radius is not None and radius[0] == "mm" and spacing is None:
+                    raise ValueError("VolumeSegmenter: an opening or closing radius in mm needs a spacing")
+        if morph_stats_out is not None:
+            if post_out is None or not morph:
+                raise ValueError("morph_stats_out needs post_out and VolumeSegmenter(opening=... or closing=...)")
+            if not (torch.is_tensor(morph_stats_out) and morph_stats_out.dtype == torch.int64 and morph_stats_out.is_contiguous()
+                    and tuple(morph_stats_out.shape) == (K - 1, 2 * MO.STATS_ROW)):
+                raise ValueError(f"morph_stats_out must be a contiguous int64 [{K - 1}, {2 * MO.STATS_ROW}] tensor")
+            if morph_stats_out.device != dev:
+                raise ValueError(f"morph_stats_out is on {morph_stats_out.device}, the net on {dev}")
         nb = -(-S // B)
         pad = nb * B - S
 
@@ -429,7 +474,7 @@ class VolumeSegmenter:
                 seg_tally(tab[2] + [appr[sl]], [0] * (T + 1) + [1], self._nv, labels[sl] if labels is not None else None, counts,
                           mask[sl], mask_src=T, K=K, _table=tab)
             surface = self._surface(mask[:S], appr[:S], labels[:S], K, surface_out, spacing) if self.surface and labels is not None else None
-            post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out, spacing, post_stats_out) if chain else None
+            post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out, spacing, post_stats_out, morph_stats_out) if chain else None
         if counts is None or counts_out is not None:
             res = VolumeResult(mask[:S], None, None)
         else:

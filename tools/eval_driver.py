@@ -105,9 +105,22 @@ def parse_min_component(value):
         raise ValueError(f"--min-component: a number of voxels or <x>mm3, got {value!r}") from None
 
 
+def parse_radius(value, flag="--opening"):
+    """--opening / --closing: None, a radius in voxels, or `<x>mm` -> (x, "mm"), which needs a spacing"""
+    if value is None:
+        return None
+    text = str(value).strip()
+    try:
+        if text.lower().endswith("mm"):
+            return (float(text[:-2]), "mm")
+        return float(text)
+    except ValueError:
+        raise ValueError(f"{flag}: a radius in voxels or <x>mm, got {value!r}") from None
+
+
 def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pred=None, graphed=True, segmenter=None, surface=False,
                        keep_largest=False, spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None,
-                       min_component=None):
+                       min_component=None, opening=None, closing=None, morph_per_slice=False):
     """`evaluate` through rpnet_amd.volume.VolumeSegmenter: the same printed lines and return value; thresholds, Dice tallies and the
     predicted mask are formed on the device, the tallies cross to the host once per volume.  save_pred: a directory that receives
     every volume's mask as <pid>_<class>.nrrd; segmenter: a VolumeSegmenter to reuse (its captured graphs live with it); surface: the
@@ -119,8 +132,11 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
     VolumeSegmenter (remove small -> keep largest -> fill holes, rpnet_amd.postprocess); the lines gain ` holes <n> (<filled> voxels
     filled)` and ` small <n> (<removed> voxels removed)` for the stages that are on, the lcc figures and save_pred describe the end of the
     chain, and min_component in mm3 is resolved under every item's spacing (a segmenter handed in must have been made with the same
-    options)."""
+    options).  opening, closing (None, voxels, ('rho', n) or (x, 'mm') under a spacing), morph_per_slice: the ball morphology of
+    VolumeSegmenter (rpnet_amd.morphology), the chain becoming open -> remove small -> keep largest -> close -> fill holes; the lines gain
+    ` open -<removed> +<added>` and ` close -<removed> +<added>` for the stages that are on."""
     from rpnet_amd import components as CC
+    from rpnet_amd import morphology as MO
     from rpnet_amd import postprocess as PP
     from rpnet_amd.volume import check_min_component
     from rpnet_amd import surface as SF
@@ -132,12 +148,20 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
         raise ValueError("evaluate_on_device: surface_tolerance is a distance in millimetres; give spacing= as well")
     holes_mode, small_min = PP.holes_mode_of(fill_holes), check_min_component(min_component)
     holes_on, small_on = holes_mode is not None, small_min is not None
-    chain = bool(conn) or holes_on or small_on
+    open_r = None if opening is None else MO.check_radius(opening, "evaluate_on_device: opening")
+    close_r = None if closing is None else MO.check_radius(closing, "evaluate_on_device: closing")
+    morph_on = open_r is not None or close_r is not None
+    chain = bool(conn) or holes_on or small_on or morph_on
     if isinstance(small_min, tuple) and spacing is None:
         raise ValueError("evaluate_on_device: min_component in mm3 needs a spacing (a triple or 'header')")
+    if any(r is not None and r[0] == "mm" for r in (open_r, close_r)) and spacing is None:
+        raise ValueError("evaluate_on_device: an opening or closing radius in mm needs a spacing (a triple or 'header')")
     seg = segmenter or VolumeSegmenter(net, batch=batch_size, graphed=graphed, surface=surface, keep_largest=conn or False,
                                        surface_tolerance=surface_tolerance, fill_holes=fill_holes, hole_connectivity=hole_connectivity,
-                                       max_hole=max_hole, min_component=min_component)
+                                       max_hole=max_hole, min_component=min_component,
+                                       **(dict(opening=opening, closing=closing, morph_per_slice=morph_per_slice) if morph_on else {}))
+    if morph_on and (seg.opening != open_r or seg.closing != close_r or seg.morph_per_slice != bool(morph_per_slice)):
+        raise ValueError("evaluate_on_device(opening=..., closing=...) needs a VolumeSegmenter made with the same options")
     if (holes_on or small_on) and (seg.fill_holes != holes_mode or seg.min_component != small_min):
         raise ValueError("evaluate_on_device(fill_holes=..., min_component=...) needs a VolumeSegmenter made with the same options")
     n_loop = len(loader) if n_items is None else min(n_items, len(loader))
@@ -153,6 +177,7 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
         raise ValueError(f"evaluate_on_device(keep_largest={conn}) needs a VolumeSegmenter(keep_largest={conn})")
     lcc_dice, lcc_fig, lcc_surf = defaultdict(list), defaultdict(list), defaultdict(list)
     holes_fig, small_fig = defaultdict(list), defaultdict(list)
+    open_fig, close_fig = defaultdict(list), defaultdict(list)
     surf_few, surf_aff = defaultdict(list), defaultdict(list)
     classes = config["eval_classes"]
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
@@ -189,6 +214,11 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
             holes_fig[name].append(h)
             small_fig[name].append(sm)
             line += PP.line_suffix(h, sm)
+        if morph_on:
+            op, cl = res.post["opening"][0] if open_r is not None else None, res.post["closing"][0] if close_r is not None else None
+            open_fig[name].append(op)
+            close_fig[name].append(cl)
+            line += MO.line_suffix(op, cl)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{s['pid']}_{name}.nrrd"), (res.post["mask"] if chain else res.mask).cpu().numpy(),
@@ -200,7 +230,9 @@ def evaluate_on_device(net, loader, config, n_items=None, batch_size=8, save_pre
                      if surface else "")
                   + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else "")
                   + (PP.mean_suffix(holes_fig[name] if holes_on else None, small_fig[name] if small_on else None)
-                     if holes_on or small_on else ""))
+                     if holes_on or small_on else "")
+                  + (MO.mean_suffix(open_fig[name] if open_r is not None else None, close_fig[name] if close_r is not None else None)
+                     if morph_on else ""))
     return dsc_affine, dsc_fewshot, dsc_ref
 
 
@@ -231,6 +263,13 @@ def build_parser():
     ap.add_argument("--min-component", default=None, metavar="VOXELS|<x>mm3",
                     help="remove the components of the final mask with fewer voxels, or below <x> cubic millimetres under --spacing (with "
                          "`header` resolved per item); implies --on-device")
+    ap.add_argument("--opening", default=None, metavar="R[mm]",
+                    help="open the final mask by a ball of this radius in voxels, or in millimetres under --spacing (rpnet_amd.morphology), "
+                         "before the component filters; implies --on-device")
+    ap.add_argument("--closing", default=None, metavar="R[mm]",
+                    help="close the final mask by a ball of this radius in voxels, or in millimetres under --spacing, before the holes are "
+                         "filled; implies --on-device")
+    ap.add_argument("--morph-slice", action="store_true", help="--opening and --closing on every slice on its own")
     return ap
 
 
@@ -246,7 +285,14 @@ def main():
         raise SystemExit("--max-hole needs --fill-holes")
     if isinstance(min_component, tuple) and spacing is None:
         raise SystemExit("--min-component <x>mm3 needs --spacing")
+    opening, closing = parse_radius(a.opening, "--opening"), parse_radius(a.closing, "--closing")
+    if any(isinstance(r, tuple) for r in (opening, closing)) and spacing is None:
+        raise SystemExit("--opening / --closing <x>mm needs --spacing")
+    if a.morph_slice and opening is None and closing is None:
+        raise SystemExit("--morph-slice needs --opening or --closing")
     post = dict(fill_holes=a.fill_holes or False, max_hole=a.max_hole, min_component=min_component)
+    if opening is not None or closing is not None:
+        post.update(opening=opening, closing=closing, morph_per_slice=a.morph_slice)
     loader = None if a.device_items else FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
     net = model_factory[args.net](pretrained_path=config.get("pretrained_path"),
                                   cfg={"align": True, "backbone": config.get("backbone", "vgg")}, backbone_cfg=config).cuda()
@@ -260,7 +306,7 @@ def main():
         source.warm()
         evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface,
                          keep_largest=a.keep_largest or False, spacing=spacing, surface_tolerance=tolerance, **post)
-    elif a.on_device or a.save_pred or a.surface or a.keep_largest or a.fill_holes or min_component is not None:
+    elif a.on_device or a.save_pred or a.surface or a.keep_largest or a.fill_holes or min_component is not None or "opening" in post:
         evaluate_on_device(net, loader, config, a.items, a.batch or 8, a.save_pred, surface=a.surface, keep_largest=a.keep_largest or False,
                            spacing=spacing, surface_tolerance=tolerance, **post)
     else:
