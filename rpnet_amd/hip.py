@@ -232,6 +232,27 @@ SIDE_ABIS = [
     ("rpnet_morph_abi.h", "morphology", "rpnet_morph_abi_version", MORPH_ABI_VERSION, _MORPH_SIGS),
 ]
 
+# body-mask preprocessing of raw volumes (threshold, seeded component, mask and box): include/rpnet_prep_abi.h (ledger:
+# tests/prep_abi_ledger.py).  The ninth side family.  tests/test_host_morph_abi_ledger.py holds SIDE_ABIS to the eight rows above with the
+# morphology row last, so the families that came after it stand in a table of their own, of the same form; load() binds and checks
+# ALL_SIDE_ABIS, and tests/test_host_prep_abi_ledger.py asserts over ALL_SIDE_ABIS what tests/test_host_side_abi_table.py asserts
+# over SIDE_ABIS.
+_PREP_SIGS = {
+    "rpnet_prep_abi_version": (ci, []),
+    "rpnet_prep_threshold_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_prep_threshold": (ci, [vp, ci, vp, ci, ci, ci, ci, cd, vp, vp, vp, cs, vp]),
+    "rpnet_prep_seeded_component_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_prep_seeded_component": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, cs, vp]),
+    "rpnet_prep_mask_bbox_workspace_bytes": (cs, [ci, ci, ci]),
+    "rpnet_prep_mask_bbox": (ci, [vp, ci, vp, vp, cd, ci, ci, ci, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+PREP_ABI_SYMBOLS = tuple(_PREP_SIGS)
+PREP_ABI_VERSION = 1     # RPNET_PREP_ABI_VERSION of include/rpnet_prep_abi.h
+LATER_SIDE_ABIS = [
+    ("rpnet_prep_abi.h", "preprocessing", "rpnet_prep_abi_version", PREP_ABI_VERSION, _PREP_SIGS),
+]
+ALL_SIDE_ABIS = SIDE_ABIS + LATER_SIDE_ABIS
+
 
 def lib_path():
     return _LIB_PATH
@@ -249,13 +270,13 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        for sigs in [_SIGS] + [family[4] for family in SIDE_ABIS]:
+        for sigs in [_SIGS] + [family[4] for family in ALL_SIDE_ABIS]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)
                 if fn is None:
                     raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
                 fn.restype, fn.argtypes = res, args
-        for header, words, version_symbol, version, _ in SIDE_ABIS:
+        for header, words, version_symbol, version, _ in ALL_SIDE_ABIS:
             if getattr(lib, version_symbol)() != version:
                 raise RuntimeError(f"{_LIB_PATH} has {words} ABI version {getattr(lib, version_symbol)()}, this binding was written for "
                                    f"{version} (include/{header}): rebuild it with `make -C rpnet_amd/csrc`")
