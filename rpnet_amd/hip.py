@@ -253,6 +253,21 @@ LATER_SIDE_ABIS = [
 ]
 ALL_SIDE_ABIS = SIDE_ABIS + LATER_SIDE_ABIS
 
+# resampling of images and label maps to another grid: include/rpnet_resample_abi.h (ledger: tests/resample_abi_ledger.py).  The tenth
+# side family.  tests/test_host_prep_abi_ledger.py holds ALL_SIDE_ABIS to the nine rows above with the preprocessing row last, so the
+# families that came after it stand in a further table of the same form; load() binds and checks ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP.
+_RESAMPLE_SIGS = {
+    "rpnet_resample_abi_version": (ci, []),
+    "rpnet_resample_workspace_bytes": (cs, [ci, ci, ci, ci, ci, ci]),
+    "rpnet_resample_image": (ci, [vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, cs, vp]),
+    "rpnet_resample_labels": (ci, [vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+RESAMPLE_ABI_SYMBOLS = tuple(_RESAMPLE_SIGS)
+RESAMPLE_ABI_VERSION = 1     # RPNET_RESAMPLE_ABI_VERSION of include/rpnet_resample_abi.h
+SIDE_ABIS_AFTER_PREP = [
+    ("rpnet_resample_abi.h", "resampling", "rpnet_resample_abi_version", RESAMPLE_ABI_VERSION, _RESAMPLE_SIGS),
+]
+
 
 def lib_path():
     return _LIB_PATH
@@ -270,13 +285,14 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        for sigs in [_SIGS] + [family[4] for family in ALL_SIDE_ABIS]:
+        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP
+        for sigs in [_SIGS] + [family[4] for family in side_abis]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)
                 if fn is None:
                     raise RuntimeError(f"{_LIB_PATH} does not export {name}: rebuild it with `make -C rpnet_amd/csrc`")
                 fn.restype, fn.argtypes = res, args
-        for header, words, version_symbol, version, _ in ALL_SIDE_ABIS:
+        for header, words, version_symbol, version, _ in side_abis:
             if getattr(lib, version_symbol)() != version:
                 raise RuntimeError(f"{_LIB_PATH} has {words} ABI version {getattr(lib, version_symbol)()}, this binding was written for "
                                    f"{version} (include/{header}): rebuild it with `make -C rpnet_amd/csrc`")

@@ -12,7 +12,8 @@ row {n_A, n_B, k, within_A, within_B} and one fp64 row {d2_k, d2_k1, d2_max, sum
 device; `figures_from_rows` turns a pair of rows into the four figures on the host; `rows_reference_spacing` restates the rows in
 numpy and is what the GPU tests compare with (tests/test_host_surface_spacing.py pins it to scipy.ndimage).
 
-Out of scope: an oblique grid is measured by the norms of its axis vectors only (`spacing_from_header`), and nothing is resampled.
+Out of scope: an oblique grid is measured by the norms of its axis vectors only (`spacing_from_header`), and nothing is resampled here
+(rpnet_amd.resample takes a volume to another spacing).
 """
 import ctypes
 import math

@@ -2,7 +2,8 @@
 (rpnet_amd.preprocess): what the reference's utils/preprocess_abd_110.py does through SimpleITK on four host processes.
 
   python tools/preprocess_volumes.py --raw-dir RAW --save-dir OUT [--radius 7] [--threshold otsu|T] [--fill -1024] [--inclusive-crop]
-                                     [--rois Liver Spleen ...]
+                                     [--rois Liver Spleen ...] [--resample Z,Y,X [--resample-align corner|center]
+                                     [--mask-interp linear|nearest]]
 
 Reads RAW/<pid>/img.nrrd and RAW/<pid>/structures/<roi>.nrrd (axes x, y, z as the reference's files have them), swaps the axes to
 [D, H, W] as the reference does, masks the volume with its body mask, crops image and structures to the box of what is left above the
@@ -12,8 +13,15 @@ used, the reference's yy.max(), xx.max(), one more with --inclusive-crop).  The 
 the output headers in the order of the swapped axes, so spacing="header" keeps working downstream.  One line per volume: the box and
 the voxels of the mask after each stage.
 
-Not written: the reference's <pid>_raw.npy and the combined _masks file; resampling and z_starts are switched off in the reference and
-absent here; DICOM input is not read."""
+--resample Z,Y,X takes the image and every structure to that spacing in millimetres (rpnet_amd.resample) before the body mask and the
+crop, in the reference's order (its do_resample): the grid is resample.output_shape of the input's shape and header spacing, the image is
+resampled trilinearly, a structure by --mask-interp: linear (the default, the reference's `resample(mask) > 0.5`; it takes the voxels of
+value 1, which is what the reference's 0 / 1 structure files hold) or nearest.  The output headers then carry the spacing the new grid
+really has (resample.out_spacing), so spacing="header" downstream reports millimetres on the new grid, and bbox.npy is formed from the
+resampled shape.  The input header must carry a spacing.  Without --resample the files are byte for byte what they were.
+
+Not written: the reference's <pid>_raw.npy and the combined _masks file; z_starts is switched off in the reference and absent here;
+DICOM input is not read."""
 import argparse
 import os
 import sys
@@ -23,6 +31,7 @@ import numpy as np
 import torch
 
 from rpnet_amd import preprocess as PP
+from rpnet_amd import resample as RS
 from rpnet_amd.surface_spacing import spacing_from_header
 from rpnet_amd.utils import nrrd
 
@@ -36,6 +45,9 @@ def build_parser():
     ap.add_argument("--fill", type=float, default=-1024, help="the value outside the mask")
     ap.add_argument("--inclusive-crop", action="store_true", help="keep the last row and column of the box (the reference drops them)")
     ap.add_argument("--rois", nargs="*", default=None, help="structure names; default: every file under structures/")
+    ap.add_argument("--resample", default=None, metavar="Z,Y,X", help="resample image and structures to this spacing in mm before the body mask")
+    ap.add_argument("--resample-align", choices=("corner", "center"), default="corner", help="which points of the two grids coincide")
+    ap.add_argument("--mask-interp", choices=("linear", "nearest"), default="linear", help="how a structure is resampled (linear: > 0.5)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -46,17 +58,46 @@ def image_array(data):
     return np.ascontiguousarray(a if a.dtype == np.int16 else a.astype(np.float32))
 
 
-def spacing_fields(header):
-    """the header fields that carry the input's spacing in the order of the swapped axes, or None when the input has none"""
-    try:
-        s = spacing_from_header(header)             # of the file's axes x, y, z
-    except ValueError:
-        return None
-    sz, sy, sx = s[2], s[1], s[0]
+def spacing_fields(header, resampled=None):
+    """the header fields that carry the input's spacing in the order of the swapped axes, or None when the input has none; resampled:
+    the (sz, sy, sx) of the new grid, written in its place"""
+    if resampled is not None:
+        sz, sy, sx = resampled
+    else:
+        try:
+            s = spacing_from_header(header)             # of the file's axes x, y, z
+        except ValueError:
+            return None
+        sz, sy, sx = s[2], s[1], s[0]
     return {"space": "left-posterior-superior", "space directions": f"({sz!r},0,0) (0,{sy!r},0) (0,0,{sx!r})"}
 
 
-def preprocess_one(pid, raw_dir, save_dir, device, radius=7, threshold="otsu", fill=-1024, inclusive_crop=False, rois=None):
+def parse_spacing(text):
+    """'Z,Y,X' -> (sz, sy, sx) in millimetres"""
+    try:
+        s = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        s = ()
+    if len(s) != 3 or not all(np.isfinite(v) and v > 0 for v in s):
+        raise SystemExit(f"--resample wants three positive numbers Z,Y,X in millimetres, got {text!r}")
+    return s
+
+
+def resample_all(pid, image, structures, header, new_spacing, align, mask_interp):
+    """the image and every structure (device tensors) at `new_spacing` -> (image, structures, the spacing of the new grid)"""
+    try:
+        s = spacing_from_header(header)
+    except ValueError as e:
+        raise ValueError(f"{pid}: --resample needs the spacing of the input and img.nrrd carries none ({e})")
+    spacing = (s[2], s[1], s[0])
+    image, grid_spacing = RS.resample_to_spacing(image, spacing, new_spacing, align=align)
+    options = {"classes": (1,), "mode": "linear"} if mask_interp == "linear" else {"mode": "nearest"}
+    structures = {roi: RS.resample_like(m, tuple(image.shape), align=align, **options) for roi, m in structures.items()}
+    return image, structures, grid_spacing
+
+
+def preprocess_one(pid, raw_dir, save_dir, device, radius=7, threshold="otsu", fill=-1024, inclusive_crop=False, rois=None, resample=None,
+                   resample_align="corner", mask_interp="linear"):
     data, header = nrrd.read(os.path.join(raw_dir, pid, "img.nrrd"))
     if data.ndim != 3:
         raise ValueError(f"{pid}: img.nrrd has {data.ndim} axes, a volume has 3")
@@ -74,16 +115,18 @@ def preprocess_one(pid, raw_dir, save_dir, device, radius=7, threshold="otsu", f
         if m.shape != image.shape:
             raise ValueError(f"{pid}: structure {roi} is {m.shape}, the image {image.shape}")
         structures[roi] = torch.from_numpy(m).to(device)
-    res = PP.clean_volume(torch.from_numpy(image).to(device), structures, fill=fill, reference_crop=not inclusive_crop, radius=radius,
-                          threshold=threshold)
+    volume, grid_spacing = torch.from_numpy(image).to(device), None
+    if resample is not None:
+        volume, structures, grid_spacing = resample_all(pid, volume, structures, header, resample, resample_align, mask_interp)
+    res = PP.clean_volume(volume, structures, fill=fill, reference_crop=not inclusive_crop, radius=radius, threshold=threshold)
     y0, y1, x0, x1 = res["box"]
-    extra = spacing_fields(header)
+    extra = spacing_fields(header, grid_spacing)
     os.makedirs(save_dir, exist_ok=True)
     clean = res["image"].cpu().numpy()
     nrrd.write(os.path.join(save_dir, f"{pid}_clean.nrrd"), clean, header=extra)
     for roi, m in res["structures"].items():
         nrrd.write(os.path.join(save_dir, f"{pid}_{roi}.nrrd"), m.cpu().numpy(), header=extra)
-    bbox = np.array([[0, y0, x0], [image.shape[0], y1, x1]])
+    bbox = np.array([[0, y0, x0], [volume.shape[0], y1, x1]])
     np.save(os.path.join(save_dir, f"{pid}_bbox.npy"), bbox)
     voxels = res["tables"]["voxels"].cpu().numpy().tolist()
     print(f"{pid} {tuple(clean.shape)} box y {y0}:{y1} x {x0}:{x1} kept " + " ".join(f"{n} {v}" for n, v in zip(PP.STAGES, voxels))
@@ -97,7 +140,9 @@ def main(argv=None):
     pids = sorted(p for p in os.listdir(a.raw_dir) if os.path.isfile(os.path.join(a.raw_dir, p, "img.nrrd")))
     if not pids:
         raise SystemExit(f"no <pid>/img.nrrd under {a.raw_dir}")
-    return [preprocess_one(pid, a.raw_dir, a.save_dir, a.device, a.radius, threshold, a.fill, a.inclusive_crop, a.rois) for pid in pids]
+    resample = None if a.resample is None else parse_spacing(a.resample)
+    return [preprocess_one(pid, a.raw_dir, a.save_dir, a.device, a.radius, threshold, a.fill, a.inclusive_crop, a.rois, resample, a.resample_align,
+                           a.mask_interp) for pid in pids]
 
 
 if __name__ == "__main__":
