@@ -9,7 +9,8 @@
 // (rpnet_conv1_fwd with y == NULL) only sums it, BatchNorm + ReLU (rpnet_conv1_bn_relu) makes it again and writes the
 // operand planes of Conv1.conv.3, and the backward's reduction pass and weight gradient (rpnet_conv1_bn_bwd_partial,
 // rpnet_conv1_wgrad_bn with y == NULL) make it again from the image.  conv1_quad is the ONE definition of a value of y
-// (explicit fused multiply-adds, taps in row-major order): a value made twice is the same bits twice.
+// (explicit fused multiply-adds, taps in row-major order), conv1_bn_dy the one definition of a value of dy: a value made twice is
+// the same bits twice.
 #include "common.h"
 #include "split_bf16.h"
 
@@ -72,6 +73,16 @@ __device__ __forceinline__ void conv1_quad4(const float* __restrict__ x, const f
                 for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(xv[ky][px + kx], wv[ky * 3 + kx][k], acc[k]);
         out[px] = acc;
     }
+}
+
+// dy of one element from the gradient dz of the layer's BatchNorm + ReLU output, y and the BatchNorm parameters, as the weight and
+// input gradients form it: dy = scale (dz [y scale + shift > 0] - c1 - xhat c2).  The ONE definition, in explicit fused multiply-adds:
+// left to the compiler, conv1_dgrad_bn_kernel<true> kept xhat c2 a product of its own while <false> and the weight gradients
+// contracted it into the subtraction, and the input gradient with y made again differed from the one with y given in its last bits.
+__device__ __forceinline__ float conv1_bn_dy(const float d, const float v, const float sc, const float sh, const float mu,
+                                             const float is, const float c1, const float c2) {
+    const float dm = (__builtin_fmaf(v, sc, sh) > 0.f) ? d : 0.f;
+    return sc * __builtin_fmaf((mu - v) * is, c2, dm - c1);      // (mu - v) is = -xhat, exactly
 }
 
 // strip s (four consecutive pixels 4 s .. 4 s + 3 of the N x H x W pixel sequence, W % 4 == 0) -> (image base, oy, ox0)
@@ -281,10 +292,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_partial(const float* __restri
                 if constexpr (RECOMP) v = conv1_quad(x, wl, Cout, q, nb, oy, ox, H, W);
                 else v = *reinterpret_cast<const f32x4*>(ybn + p * Cout + q * 4);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float dm = (v[k] * sc[k] + sh[k] > 0.f) ? gr[k] : 0.f;
-                    gr[k] = sc[k] * (dm - c1[k] - (v[k] - mu[k]) * is[k] * c2[k]);
-                }
+                for (int k = 0; k < 4; ++k) gr[k] = conv1_bn_dy(gr[k], v[k], sc[k], sh[k], mu[k], is[k], c1[k], c2[k]);
             }
 #pragma unroll
             for (int ky = -1; ky <= 1; ++ky)
@@ -370,10 +378,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_partial4(const float* __restr
                     if constexpr (RECOMP) v = v4[px];
                     else v = *reinterpret_cast<const f32x4*>(ybn + e);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float dm = (v[k] * sc[k] + sh[k] > 0.f) ? gr[k] : 0.f;
-                        gr[k] = sc[k] * (dm - c1[k] - (v[k] - mu[k]) * is[k] * c2[k]);
-                    }
+                    for (int k = 0; k < 4; ++k) gr[k] = conv1_bn_dy(gr[k], v[k], sc[k], sh[k], mu[k], is[k], c1[k], c2[k]);
                 }
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky)
@@ -684,11 +689,9 @@ __global__ __launch_bounds__(256) void conv1_dgrad_bn_kernel(const float* __rest
                 if constexpr (RECOMP) v = conv1_quad(x, wl, Cout, c / 4, nb, hy, hx, H, W);
                 else v = *reinterpret_cast<const f32x4*>(ybn + p * Cout + c);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float sc = prm[c + k], sh = prm[Cout + c + k], mu = prm[2 * Cout + c + k], is = prm[3 * Cout + c + k];
-                    const float dm = (v[k] * sc + sh > 0.f) ? d[k] : 0.f;
-                    r[k] = sc * (dm - prm[4 * Cout + c + k] - (v[k] - mu) * is * prm[5 * Cout + c + k]);
-                }
+                for (int k = 0; k < 4; ++k)
+                    r[k] = conv1_bn_dy(d[k], v[k], prm[c + k], prm[Cout + c + k], prm[2 * Cout + c + k], prm[3 * Cout + c + k],
+                                       prm[4 * Cout + c + k], prm[5 * Cout + c + k]);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) dyl[(q * 4 + k) * kC1dPix + pix] = r[k];

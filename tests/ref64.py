@@ -278,3 +278,50 @@ def conv_wgrad(x0, x1, dy, taps=9, dilation=1, upsample=0, in_scale=None, in_sca
     xp = F.pad(x, (0, 0, d, d, d, d))
     return torch.stack([torch.stack([torch.einsum("nhwi,nhwo->oi", xp[:, kh * d:kh * d + H, kw * d:kw * d + W], dy)
                                      for kw in range(3)], -1) for kh in range(3)], -2)
+
+
+# ------------------------- the first layer, Cin = 1 (Conv1.conv.0 of net/unet.py:407 with img_ch = 1, conv_block of net/modules.py:47-49)
+def _per_image(v, N):
+    """[groups, C] -> [N, 1, 1, C]: image n is in statistic group n // (N // groups)"""
+    return v.repeat_interleave(N // v.shape[0], 0)[:, None, None]
+
+
+def conv1(x, w, bias=None, dtype=F64):
+    """x [N, H, W] (= [N, 1, H, W]), w [cout, 1, 3, 3], bias [cout] or None -> y [N, H, W, cout] = nn.Conv2d(1, cout, 3, padding=1)"""
+    return _nhwc(F.conv2d(_c(x, dtype)[:, None], _c(w, dtype), _c(bias, dtype), padding=1))
+
+
+def conv1_affine_relu(y, scale, shift, groups=1, dtype=F64):
+    """relu(y * scale[g] + shift[g]), y [N, H, W, C], scale / shift [groups, C] (or [C] with groups = 1: the eval-mode epilogue)"""
+    y = _c(y, dtype)
+    sc, sh = _c(scale, dtype).reshape(groups, -1), _c(shift, dtype).reshape(groups, -1)
+    return torch.relu(y * _per_image(sc, y.shape[0]) + _per_image(sh, y.shape[0]))
+
+
+def _bn_terms(dz, y, stats, groups, dtype):
+    """(dz m, xhat) with m = [y scale + shift > 0], xhat = (y - mean) invstd; stats [4][groups][C] = scale, shift, mean, invstd"""
+    dz, y, st = _c(dz, dtype), _c(y, dtype), _c(stats, dtype).reshape(4, groups, -1)
+    N = y.shape[0]
+    sc, sh, mu, inv = (_per_image(st[i], N) for i in range(4))
+    return dz * (y * sc + sh > 0).to(dtype), (y - mu) * inv, sc
+
+
+def bn_bwd_sums(dz, y, stats, groups=1, dtype=F64):
+    """-> (sum dz m, sum dz m xhat), each [groups, C]: the two sums of the BatchNorm + ReLU backward per (group, channel)"""
+    dm, xhat, _ = _bn_terms(dz, y, stats, groups, dtype)
+    C = dm.shape[-1]
+    return dm.reshape(groups, -1, C).sum(1), (dm * xhat).reshape(groups, -1, C).sum(1)
+
+
+def bn_dy(dz, y, stats, coef=None, groups=1, dtype=F64):
+    """dy = scale (dz m - c1 - xhat c2), coef [groups, C, 2] = (c1, c2) (None: zero, the eval-mode form) -> [N, H, W, C]"""
+    dm, xhat, sc = _bn_terms(dz, y, stats, groups, dtype)
+    if coef is None:
+        return sc * dm
+    cf = _c(coef, dtype).reshape(groups, -1, 2)
+    return sc * (dm - _per_image(cf[..., 0], dm.shape[0]) - xhat * _per_image(cf[..., 1], dm.shape[0]))
+
+
+def conv1_dgrad(dy, w, dtype=F64):
+    """dy [N, H, W, cout], w [cout, 1, 3, 3] -> dx [N, H, W]: the adjoint of conv1 with respect to the image"""
+    return F.conv_transpose2d(_c(dy, dtype).permute(0, 3, 1, 2), _c(w, dtype), padding=1)[:, 0]

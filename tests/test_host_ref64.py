@@ -137,3 +137,33 @@ def test_conv_wgrad_is_autograd_of_conv2d(taps, dilation, upsample, mode, two):
     (want,) = torch.autograd.grad(y, wt, dy.double().permute(0, 3, 1, 2))
     assert got.shape == want.shape and rel_err(got, want) < 1e-14
     assert R.conv_wgrad(x0, x1, dy, taps, dilation, upsample, s if mode else None, mode, dtype=torch.float32).dtype == torch.float32
+
+
+@pytest.mark.parametrize("groups", [1, 2])
+def test_first_layer_references_are_autograd_of_conv_bn_relu(groups):
+    """the pin of R.conv1, conv1_affine_relu, bn_bwd_sums, bn_dy and conv1_dgrad: autograd of nn.Conv2d(1, C, 3, padding=1) ->
+    nn.BatchNorm2d (train mode, one batch per statistic group) -> nn.ReLU in float64"""
+    import torch.nn.functional as F
+    N, H, W, C, eps = 4, 5, 7, 6, 1e-5
+    x, w, b = rnd(911, N, H, W).double(), rnd(912, C, 1, 3, 3).double(), rnd(913, C).double()
+    gamma, beta, dz = 1 + 0.1 * rnd(914, C).double(), 0.1 * rnd(915, C).double(), rnd(916, N, H, W, C).double()
+    xr, wr, gr, br = (t.clone().requires_grad_(True) for t in (x, w, gamma, beta))
+    n = N // groups
+    ys = [F.conv2d(xr[g * n:(g + 1) * n, None], wr, b, padding=1) for g in range(groups)]
+    z = torch.cat([torch.relu(F.batch_norm(y, None, None, gr, br, True, 0.1, eps)) for y in ys]).permute(0, 2, 3, 1)
+    dx, dw, dg, db = torch.autograd.grad(z, (xr, wr, gr, br), dz)
+    y = R.conv1(x, w, b)
+    assert rel_err(y, torch.cat(ys).permute(0, 2, 3, 1)) < 1e-12
+    yg = y.reshape(groups, -1, C)
+    mean, var = yg.mean(1), yg.var(1, unbiased=False)
+    invstd = (var + eps).rsqrt()
+    stats = torch.stack([gamma * invstd, beta - mean * gamma * invstd, mean, invstd])
+    assert rel_err(R.conv1_affine_relu(y, stats[0], stats[1], groups), z) < 1e-12
+    s1, s2 = R.bn_bwd_sums(dz, y, stats, groups)
+    assert rel_err(s1.sum(0), db) < 1e-12 and rel_err(s2.sum(0), dg) < 1e-12
+    dy = R.bn_dy(dz, y, stats, torch.stack([s1, s2], -1) / (n * H * W), groups)
+    assert rel_err(R.conv1_dgrad(dy, w), dx) < 1e-12
+    assert rel_err(R.conv_wgrad(x[..., None], None, dy), dw) < 1e-12
+    # coef None: nothing subtracted (eval mode); float32 is the same code
+    assert torch.equal(R.bn_dy(dz, y, stats, None, groups), R.bn_dy(dz, y, stats, torch.zeros(groups, C, 2), groups))
+    assert R.conv1(x, w, b, dtype=torch.float32).dtype == torch.float32 and R.conv1_dgrad(dy, w, dtype=torch.float32).dtype == torch.float32
