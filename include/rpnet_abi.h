@@ -53,7 +53,10 @@ enum rpnet_status {
  * against.  109: rpnet_bn_eval_relu, rpnet_bn_eval_bwd, rpnet_conv1_dgrad_bn added (the gradient through eval-mode BatchNorm and the
  * input images' gradient); nothing existing changed.  110: rpnet_seg_tally added (masks and Dice tallies of an evaluation call);
  * nothing existing changed.  111: rpnet_slice_minmax, rpnet_augment_affine, rpnet_elastic_field, rpnet_elastic_apply added (train-time
- * augmentation of episode slices); nothing existing changed. */
+ * augmentation of episode slices); nothing existing changed.  Still 111: rpnet_split_f16, rpnet_pack_conv_weight and
+ * rpnet_pack_conv_weights_split refuse calls that their contract already excluded (s_b with a_is_bound; channel ranges that are
+ * negative, overlap or do not fit cin_pad), and rpnet_predict_scales counts a NaN measurement as a violation; no signature, layout or
+ * accepted call changed. */
 #define RPNET_ABI_VERSION 111
 int rpnet_version(void);
 const char* rpnet_last_error_string(void);
@@ -64,7 +67,11 @@ const char* rpnet_last_error_string(void);
  *   wd  [taps][Cout/4][Cin_pad][4]  dgrad B operand: taps flipped, Cin/Cout swapped
  * `cin_off`/`cin_pad`: input channel c of the weight lands on packed row cin_off + c of
  * cin_pad rows; the other rows are zero (the 121 correlation channels are padded to 128,
- * net/rp_net.py:65-69,81).  wd may be NULL. taps = 9 (3x3) or 1 (1x1). */
+ * net/rp_net.py:65-69,81).  wd may be NULL. taps = 9 (3x3) or 1 (1x1).
+ * Source channel c lands on row cin_off0 + c for c < cin_split, else on row cin_off1 + (c - cin_split).  Refused (RPNET_ERR_SHAPE,
+ * here and in the split packs below): cin <= 0, cin_split outside 0 .. cin, a negative offset, a range that does not fit cin_pad,
+ * two non-empty ranges that share a row.  The kernels write the rows of the two ranges only; the caller zeroes the others
+ * (the gathering form of the split pack writes its zero rows itself). */
 int rpnet_pack_conv_weight(const float* w, float* wp, float* wd, int cout, int cin, int taps,
                            int cin_off0, int cin_split, int cin_off1, int cin_pad, rpnet_stream_t stream);
 
@@ -90,13 +97,21 @@ int rpnet_pack_conv_weight(const float* w, float* wp, float* wd, int cout, int c
  *   wp [planes][taps][Cin_pad/32][Cout][32]   (k = input channel, contiguous per output channel)
  *   wd [planes][taps][Cout/32][Cin_pad][32]   (dgrad: k = output channel, taps flipped); wd may be NULL.
  * cin_pad, cout multiples of 32; channel ranges that are not multiples of 8 (the 377 = 121 + 256 channels of the 1x1
- * convolution, packed as 128 + 256) take a gathering form of the kernel. */
+ * convolution, packed as 128 + 256) take a gathering form of the kernel.
+ * rows == 0 is accepted and writes nothing (*s_out included).
+ * Alignment: x, out and every plane of out (rows * C elements apart) are read / written as 16-byte vectors and must be 16-byte
+ * aligned; so must wp / wd of the split packs and wc of rpnet_upconv_collapse_weights.
+ * Padding: the plain form of the pack kernel (every range a multiple of 8) writes the rows of the two channel ranges only, and the
+ * caller zeroes the others once; the gathering form writes all cin_pad rows of wp and wd, the padding rows as zeros, and for
+ * planes <= 2 divides the wd padding rows by the caller's preset row_scale_wd (any finite non-zero value; never written). */
 int rpnet_split_bf16(const float* x, const float* scale, int scale_mode, void* out, size_t rows, int C, int planes,
                      rpnet_stream_t stream);
-/* *s_out = the power-of-two tensor scale for a tensor bounded by *bound (maps the bound to <= 2^15); see out_absmax */
+/* *s_out = the power-of-two tensor scale for a tensor bounded by *bound (maps the bound to <= 2^15); see out_absmax.
+ * s = 2^(ceil(log2 bound) - 15), clamped to 2^-100 .. 2^100: a bound that is zero, negative, NaN or below 2^-85 gives 2^-100.
+ * Above 2^115 (+inf included) the scale stays 2^100 and no longer maps the bound to 2^15: such a bound must not scale data. */
 /* Predicted fp16 tensor scales for eval-mode layers (running statistics give no a-priori bound, net/modules.py:48): slot i of
  * `measured` holds max |output| of layer launch i of the call that just ended (rpnet_conv_desc.out_absmax).  For i < n:
- * if check != 0 and measured[i] > bound[i] (the bound the call RAN with), *violations is incremented — the caller must redo
+ * if check != 0 and not measured[i] <= bound[i] (the bound the call RAN with; a NaN measurement counts), *violations is incremented — the caller must redo
  * the call on measured scales; then bound[i] = pow2ceil(measured[i] * safety), scale[i] = bound[i] * 2^-15 for the next call. */
 int rpnet_predict_scales(const float* measured, float* bound, float* scale, int n, float safety, int check, int* violations,
                          rpnet_stream_t stream);
@@ -104,7 +119,7 @@ int rpnet_pow2_scale(const float* bound, float* s_out, rpnet_stream_t stream);
 int rpnet_split_f16(const float* x, const float* mask, int mask_mode, const float* s_a, const float* s_b, float* s_out,
                     void* out, size_t rows, int C, int planes /* 2, or 1: plain fp16 (RPNET_CONV_MATH=f16) */,
                     int a_is_bound /* 1: *s_a is a measured bound of |x| (rpnet_conv_desc.out_absmax), s = its power-of-two
-                                      scale; s_b must be NULL */,
+                                      scale; s_b must be NULL (RPNET_ERR_ARG otherwise) */,
                     rpnet_stream_t stream);
 int rpnet_pack_conv_weight_split(const float* w, void* wp, void* wd, int cout, int cin, int taps, int cin_off0,
                                  int cin_split, int cin_off1, int cin_pad, int planes, float* row_scale_wp,

@@ -24,6 +24,13 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// the two packed row ranges of a weight pack, [off0, off0 + split) and [off1, off1 + cin - split), share no row (an empty range
+// shares none wherever it stands)
+static inline bool pack_ranges_disjoint(int cin, int off0, int split, int off1) {
+    const long n0 = split, n1 = (long)cin - split;
+    return n0 <= 0 || n1 <= 0 || off0 + n0 <= off1 || off1 + n1 <= off0;
+}
+
 // 64-lane wavefront reductions (CDNA: wave = 64)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -73,8 +73,14 @@ __global__ __launch_bounds__(256) void split_f16_kernel(const float* __restrict_
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] *= f;
         }
+        // The product stays a value of its own (the empty asm is opaque to the compiler and emits nothing): otherwise the two
+        // roundings are selected as fused fp16(v * inv + 0) and fp16(v * inv - h), which turn the planes of a -0 (a negative x times a
+        // zero mask) into h = +0, l = -0.  IEEE rounding of x f / s gives h = -0, l = +0, bit for bit the host's planes.
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] *= inv;
+        for (int q = 0; q < 8; ++q) {
+            v[q] *= inv;
+            asm("" : "+v"(v[q]));
+        }
         u32x4 o[NP];
         split8<NP>(v, o);
 #pragma unroll
@@ -91,7 +97,7 @@ __global__ __launch_bounds__(256) void predict_scales_kernel(const float* __rest
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float m = measured[i];
-    if (check && m > bound[i]) atomicAdd(violations, 1);
+    if (check && !(m <= bound[i])) atomicAdd(violations, 1);      // a NaN measurement is a violation too
     const float s = pow2_scale(m * safety);
     scale[i] = s;
     bound[i] = s * 32768.f;
@@ -1091,6 +1097,7 @@ extern "C" int rpnet_split_f16(const float* x, const float* mask, int mask_mode,
     RPNET_REQUIRE(x && out && s_a && (mask_mode == 0 || mask), RPNET_ERR_ARG, "split_f16: null pointer");
     RPNET_REQUIRE(C > 0 && C % 8 == 0 && mask_mode >= 0 && mask_mode <= 2 && (planes == 1 || planes == 2), RPNET_ERR_SHAPE,
                   "split_f16: C=%d mode=%d planes=%d", C, mask_mode, planes);
+    RPNET_REQUIRE(!a_is_bound || !s_b, RPNET_ERR_ARG, "split_f16: s_b must be NULL when *s_a is a bound (a_is_bound)");
     if (rows == 0) return RPNET_OK;
     const size_t n8 = rows * (size_t)(C / 8);
     RPNET_REQUIRE(n8 < kIndex32, RPNET_ERR_SHAPE, "split: %zu elements do not fit the 32-bit index arithmetic", n8);
@@ -1115,10 +1122,15 @@ extern "C" int rpnet_pack_conv_weights_split(const rpnet_pack_item* items, int n
         RPNET_REQUIRE(q.w && q.wp, RPNET_ERR_ARG, "pack_conv_weights_split: null pointer (item %d)", i);
         RPNET_REQUIRE(planes == 3 || (q.row_scale_wp && q.row_scale_wd), RPNET_ERR_ARG,
                       "pack_conv_weights_split: fp16 planes (1 or 2) need the row scale outputs (item %d)", i);
-        RPNET_REQUIRE(q.cout % 32 == 0 && q.cin_pad % 32 == 0 && (q.taps == 9 || q.taps == 1 || q.taps == 4), RPNET_ERR_SHAPE,
+        RPNET_REQUIRE(q.cout > 0 && q.cout % 32 == 0 && q.cin_pad % 32 == 0 && (q.taps == 9 || q.taps == 1 || q.taps == 4), RPNET_ERR_SHAPE,
                       "pack_conv_weights_split: cout %d cin_pad %d taps %d (item %d)", q.cout, q.cin_pad, q.taps, i);
-        RPNET_REQUIRE(q.cin_off0 + q.cin_split <= q.cin_pad && q.cin_off1 + (q.cin - q.cin_split) <= q.cin_pad, RPNET_ERR_SHAPE,
+        RPNET_REQUIRE(q.cin > 0 && q.cin_split >= 0 && q.cin_split <= q.cin && q.cin_off0 >= 0 && q.cin_off1 >= 0, RPNET_ERR_SHAPE,
+                      "pack_conv_weights_split: cin %d cin_split %d cin_off0 %d cin_off1 %d (item %d)", q.cin, q.cin_split, q.cin_off0,
+                      q.cin_off1, i);
+        RPNET_REQUIRE((long)q.cin_off0 + q.cin_split <= q.cin_pad && (long)q.cin_off1 + (q.cin - q.cin_split) <= q.cin_pad, RPNET_ERR_SHAPE,
                       "pack_conv_weights_split: channel ranges exceed cin_pad (item %d)", i);
+        RPNET_REQUIRE(pack_ranges_disjoint(q.cin, q.cin_off0, q.cin_split, q.cin_off1), RPNET_ERR_SHAPE,
+                      "pack_conv_weights_split: channel ranges overlap (item %d)", i);
         pk.it[i] = q;
         max_rows = std::max(max_rows, q.cout + q.cin);
         max_tiles = std::max(max_tiles, (pack_needs_gather(q) ? q.cin_pad / 32 : cdiv(q.cin, 32)) * (q.cout / 32));

@@ -592,8 +592,13 @@ extern "C" int rpnet_pack_conv_weight(const float* w, float* wp, float* wd, int 
                                       int cin_split, int cin_off1, int cin_pad, rpnet_stream_t stream) {
     using namespace rpnet;
     RPNET_REQUIRE(w && wp, RPNET_ERR_ARG, "pack_conv_weight: null pointer");
-    RPNET_REQUIRE(cout % 32 == 0 && cin_pad % 4 == 0 && (taps == 9 || taps == 1), RPNET_ERR_SHAPE,
+    RPNET_REQUIRE(cout > 0 && cout % 32 == 0 && cin_pad % 4 == 0 && (taps == 9 || taps == 1), RPNET_ERR_SHAPE,
                   "pack_conv_weight: cout %d cin_pad %d taps %d", cout, cin_pad, taps);
+    RPNET_REQUIRE(cin > 0 && cin_split >= 0 && cin_split <= cin && cin_off0 >= 0 && cin_off1 >= 0, RPNET_ERR_SHAPE,
+                  "pack_conv_weight: cin %d cin_split %d cin_off0 %d cin_off1 %d", cin, cin_split, cin_off0, cin_off1);
+    RPNET_REQUIRE((long)cin_off0 + cin_split <= cin_pad && (long)cin_off1 + (cin - cin_split) <= cin_pad, RPNET_ERR_SHAPE,
+                  "pack_conv_weight: channel ranges exceed cin_pad");
+    RPNET_REQUIRE(pack_ranges_disjoint(cin, cin_off0, cin_split, cin_off1), RPNET_ERR_SHAPE, "pack_conv_weight: channel ranges overlap");
     hipLaunchKernelGGL(pack_weight_kernel, dim3(cdiv(cin, 32), cout / 32), dim3(256), 0, (hipStream_t)stream, w, wp, wd,
                        taps, cin_pad, cout, cin, cin_off0, cin_split, cin_off1);
     return check_launch("pack_conv_weight");

@@ -90,6 +90,8 @@ def pow2_scale(bound):
     """the smallest power of two >= bound, times 2^-15 (csrc/split_bf16.h): |x / s| <= 2^15"""
     if not bound > 0:
         return 2.0 ** -100
+    if math.isinf(float(bound)):              # frexp(inf) has no exponent; the clamp is 2^100 (tests/operand_cases.py pins both ends)
+        return 2.0 ** 100
     m, e = math.frexp(float(bound))           # bound = m 2^e, 0.5 <= m < 1
     e = e - 1 if m == 0.5 else e
     return 2.0 ** max(-100, min(100, e - 15))
