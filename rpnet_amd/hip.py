@@ -268,6 +268,21 @@ SIDE_ABIS_AFTER_PREP = [
     ("rpnet_resample_abi.h", "resampling", "rpnet_resample_abi_version", RESAMPLE_ABI_VERSION, _RESAMPLE_SIGS),
 ]
 
+# separable Gaussian smoothing of a volume, the prefilter of a shrinking resample: include/rpnet_smooth_abi.h (ledger:
+# tests/smooth_abi_ledger.py).  The eleventh side family.  tests/test_host_resample_abi_ledger.py holds SIDE_ABIS_AFTER_PREP to the one
+# row above, so this family stands in a further table of the same form; load() binds and checks ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP +
+# SIDE_ABIS_AFTER_RESAMPLE.
+_SMOOTH_SIGS = {
+    "rpnet_smooth_abi_version": (ci, []),
+    "rpnet_smooth_workspace_bytes": (cs, [ci, ci, ci, ci, ci, ci]),
+    "rpnet_smooth_image": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, ci, ci, vp, cs, vp]),
+}
+SMOOTH_ABI_SYMBOLS = tuple(_SMOOTH_SIGS)
+SMOOTH_ABI_VERSION = 1     # RPNET_SMOOTH_ABI_VERSION of include/rpnet_smooth_abi.h
+SIDE_ABIS_AFTER_RESAMPLE = [
+    ("rpnet_smooth_abi.h", "smoothing", "rpnet_smooth_abi_version", SMOOTH_ABI_VERSION, _SMOOTH_SIGS),
+]
+
 
 def lib_path():
     return _LIB_PATH
@@ -285,7 +300,7 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP
+        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE
         for sigs in [_SIGS] + [family[4] for family in side_abis]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)

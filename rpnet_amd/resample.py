@@ -18,12 +18,16 @@ Labels, nearest: the label at the nearest voxel.  Labels, linear, one class per 
 voxel is of the class when the result is > 0.5 (exactly 0.5 is not); the first class writes cls or 0, every further class takes only the
 voxels that hold 0 (merge).  The statistics row of a class: int64 {voxels_in, voxels_out, out_voxels_total, 0}.
 
-Not done: no anti-aliasing filter when shrinking (scipy has none either), no oblique grids, no spline order above 1.
+Anti-aliasing (`antialias=True` of resample_image and resample_to_spacing): the image is first smoothed by rpnet_amd.smooth with the sigmas
+of smooth.antialias_sigma (an axis that shrinks from n to m voxels: (n / m - 1) / 2 voxels; this project's own rule) under the border
+"nearest", the border the coordinate clamp above implies, and the smoothed copy is resampled.  Label maps keep the indicator rule.
+
+Not done: no oblique grids, no spline order above 1.
 """
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, smooth
 from ._volume_checks import WorkspaceCache, check_table, one_device
 from .surface_spacing import check_spacing
 
@@ -35,6 +39,7 @@ STATS_ROW = 4                                       # RPNET_RESAMPLE_STATS_ROW
 MAX_DIM = 1024                                      # RPNET_CC_MAX_DIM
 RUN = {torch.float32: 4, torch.int16: 8, torch.uint8: 16}      # output x positions of a lane: 16 bytes
 _workspaces = WorkspaceCache(by_shape=False)
+_smoothed = {}                                      # (device, dtype) -> the flat intermediate an anti-aliased resample smooths into
 
 
 def check_grid(shape, fn, what="shape"):
@@ -90,10 +95,23 @@ def _resample_out(out, vol, shape, fn):
     return out
 
 
-def resample_image(vol, shape, order=1, align="corner", out=None):
+def _antialiased(vol, shape):
+    """`vol` smoothed for a resample to `shape` into the cached intermediate of its kind; `vol` itself where no axis shrinks.  The
+    intermediate is one buffer per device and kind, grown on demand (as the workspaces are: a captured graph holds the one it was
+    captured with, so capture after the largest volume has been seen)."""
+    sigma = smooth.antialias_sigma(vol.shape, shape)
+    if not any(sigma):
+        return vol
+    key = (vol.device, vol.dtype)
+    if key not in _smoothed or _smoothed[key].numel() < vol.numel():
+        _smoothed[key] = torch.empty(vol.numel(), device=vol.device, dtype=vol.dtype)
+    return smooth.smooth_image(vol, sigma, mode="nearest", out=_smoothed[key][:vol.numel()].view(vol.shape))
+
+
+def resample_image(vol, shape, order=1, align="corner", out=None, antialias=False):
     """`vol` (float32 or int16 [D,H,W]) on the grid `shape`, one `rpnet_resample_image` call on the current stream -> out, of the kind of
-    `vol`.  order: 1 trilinear, 0 nearest neighbour.  align: "corner" or "center" (the definitions above).  Launches only: nothing is
-    copied or synchronised."""
+    `vol`.  order: 1 trilinear, 0 nearest neighbour.  align: "corner" or "center" (the definitions above).  antialias: smooth the axes
+    that shrink first (one more call, into an intermediate that stays allocated).  Launches only: nothing is copied or synchronised."""
     fn = "resample_image"
     hip.require_gpu(vol, out)
     _resample_volume_check(vol, IMAGE_KINDS, "vol", fn)
@@ -103,6 +121,8 @@ def resample_image(vol, shape, order=1, align="corner", out=None):
     a = check_align(align, fn)
     out = _resample_out(out, vol, shape, fn)
     one_device(fn, vol, out, what="the volumes")
+    if antialias:
+        vol = _antialiased(vol, shape)
     dims = tuple(vol.shape) + shape
     ws, nbytes = _workspaces.get("rpnet_resample_workspace_bytes", vol.device, dims)
     hip.call("rpnet_resample_image", hip.ptr(vol), IMAGE_KINDS[vol.dtype], *dims[:3], hip.ptr(out), *shape, a, int(order), hip.ptr(ws), nbytes)
@@ -154,8 +174,11 @@ def resample_labels(mask, shape, classes=None, mode="nearest", align="corner", o
 
 def resample_like(x, ref_shape, **options):
     """`x` on the grid `ref_shape`, e.g. a prediction taken back to the native grid of its volume: resample_labels for a uint8 tensor
-    (options: classes, mode, align, out, stats; the statistics are dropped), resample_image otherwise (options: order, align, out)."""
+    (options: classes, mode, align, out, stats; the statistics are dropped), resample_image otherwise (options: order, align, out,
+    antialias).  A label map is not smoothed: antialias=True with one is refused."""
     if torch.is_tensor(x) and x.dtype == torch.uint8:
+        if options.pop("antialias", False):
+            raise ValueError("resample_like: antialias smooths an image; a uint8 label map keeps the indicator rule")
         return resample_labels(x, ref_shape, **options)[0]
     return resample_image(x, ref_shape, **options)
 
@@ -164,7 +187,7 @@ def resample_to_spacing(vol, spacing, new_spacing, align="corner", **options):
     """`vol` with the per-axis `spacing` (sz, sy, sx) taken to `new_spacing` -> (out, out_spacing).  The grid is output_shape(vol.shape,
     spacing, new_spacing); `out_spacing` is what that grid really has (the lengths are whole numbers, so it is close to `new_spacing`,
     not equal): out_spacing(...) above.  A uint8 tensor is a label map (options of resample_labels), anything else an image (options
-    of resample_image).  Launches only."""
+    of resample_image, antialias=True among them: the axes that shrink are smoothed first).  Launches only."""
     if not torch.is_tensor(vol) or vol.dim() != 3:
         raise ValueError("resample_to_spacing: vol must be a [D,H,W] tensor")
     shape = output_shape(vol.shape, spacing, new_spacing)

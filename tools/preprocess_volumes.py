@@ -3,7 +3,7 @@
 
   python tools/preprocess_volumes.py --raw-dir RAW --save-dir OUT [--radius 7] [--threshold otsu|T] [--fill -1024] [--inclusive-crop]
                                      [--rois Liver Spleen ...] [--resample Z,Y,X [--resample-align corner|center]
-                                     [--mask-interp linear|nearest]]
+                                     [--mask-interp linear|nearest] [--antialias]]
 
 Reads RAW/<pid>/img.nrrd and RAW/<pid>/structures/<roi>.nrrd (axes x, y, z as the reference's files have them), swaps the axes to
 [D, H, W] as the reference does, masks the volume with its body mask, crops image and structures to the box of what is left above the
@@ -19,6 +19,10 @@ resampled trilinearly, a structure by --mask-interp: linear (the default, the re
 value 1, which is what the reference's 0 / 1 structure files hold) or nearest.  The output headers then carry the spacing the new grid
 really has (resample.out_spacing), so spacing="header" downstream reports millimetres on the new grid, and bbox.npy is formed from the
 resampled shape.  The input header must carry a spacing.  Without --resample the files are byte for byte what they were.
+--antialias (read with --resample, on the image only) smooths every axis of the image that shrinks before it is resampled
+(rpnet_amd.smooth: a Gaussian of (n / m - 1) / 2 voxels on an axis that goes from n to m, border "nearest"), so that what lies above the
+new grid's Nyquist limit does not fold into the image; the structures keep the indicator rule.  Without it the files are byte for byte
+what --resample alone writes.
 
 Not written: the reference's <pid>_raw.npy and the combined _masks file; z_starts is switched off in the reference and absent here;
 DICOM input is not read."""
@@ -48,6 +52,7 @@ def build_parser():
     ap.add_argument("--resample", default=None, metavar="Z,Y,X", help="resample image and structures to this spacing in mm before the body mask")
     ap.add_argument("--resample-align", choices=("corner", "center"), default="corner", help="which points of the two grids coincide")
     ap.add_argument("--mask-interp", choices=("linear", "nearest"), default="linear", help="how a structure is resampled (linear: > 0.5)")
+    ap.add_argument("--antialias", action="store_true", help="with --resample: smooth the axes of the image that shrink before resampling it")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -83,21 +88,22 @@ def parse_spacing(text):
     return s
 
 
-def resample_all(pid, image, structures, header, new_spacing, align, mask_interp):
-    """the image and every structure (device tensors) at `new_spacing` -> (image, structures, the spacing of the new grid)"""
+def resample_all(pid, image, structures, header, new_spacing, align, mask_interp, antialias=False):
+    """the image and every structure (device tensors) at `new_spacing` -> (image, structures, the spacing of the new grid); antialias:
+    the image is smoothed on the axes that shrink first"""
     try:
         s = spacing_from_header(header)
     except ValueError as e:
         raise ValueError(f"{pid}: --resample needs the spacing of the input and img.nrrd carries none ({e})")
     spacing = (s[2], s[1], s[0])
-    image, grid_spacing = RS.resample_to_spacing(image, spacing, new_spacing, align=align)
+    image, grid_spacing = RS.resample_to_spacing(image, spacing, new_spacing, align=align, **({"antialias": True} if antialias else {}))
     options = {"classes": (1,), "mode": "linear"} if mask_interp == "linear" else {"mode": "nearest"}
     structures = {roi: RS.resample_like(m, tuple(image.shape), align=align, **options) for roi, m in structures.items()}
     return image, structures, grid_spacing
 
 
 def preprocess_one(pid, raw_dir, save_dir, device, radius=7, threshold="otsu", fill=-1024, inclusive_crop=False, rois=None, resample=None,
-                   resample_align="corner", mask_interp="linear"):
+                   resample_align="corner", mask_interp="linear", antialias=False):
     data, header = nrrd.read(os.path.join(raw_dir, pid, "img.nrrd"))
     if data.ndim != 3:
         raise ValueError(f"{pid}: img.nrrd has {data.ndim} axes, a volume has 3")
@@ -117,7 +123,7 @@ def preprocess_one(pid, raw_dir, save_dir, device, radius=7, threshold="otsu", f
         structures[roi] = torch.from_numpy(m).to(device)
     volume, grid_spacing = torch.from_numpy(image).to(device), None
     if resample is not None:
-        volume, structures, grid_spacing = resample_all(pid, volume, structures, header, resample, resample_align, mask_interp)
+        volume, structures, grid_spacing = resample_all(pid, volume, structures, header, resample, resample_align, mask_interp, antialias)
     res = PP.clean_volume(volume, structures, fill=fill, reference_crop=not inclusive_crop, radius=radius, threshold=threshold)
     y0, y1, x0, x1 = res["box"]
     extra = spacing_fields(header, grid_spacing)
@@ -141,8 +147,10 @@ def main(argv=None):
     if not pids:
         raise SystemExit(f"no <pid>/img.nrrd under {a.raw_dir}")
     resample = None if a.resample is None else parse_spacing(a.resample)
+    if a.antialias and resample is None:
+        raise SystemExit("--antialias is read with --resample: there is nothing to prefilter without it")
     return [preprocess_one(pid, a.raw_dir, a.save_dir, a.device, a.radius, threshold, a.fill, a.inclusive_crop, a.rois, resample, a.resample_align,
-                           a.mask_interp) for pid in pids]
+                           a.mask_interp, a.antialias) for pid in pids]
 
 
 if __name__ == "__main__":
