@@ -804,7 +804,8 @@ static int bn_check(const char* who, int N, int HW, int C, int groups) {
     using namespace rpnet;
     RPNET_REQUIRE(C % 4 == 0 && C / 4 <= 256, RPNET_ERR_SHAPE, "%s: C=%d must be a multiple of 4 and <= 1024", who, C);
     RPNET_REQUIRE(groups >= 1 && N % groups == 0, RPNET_ERR_SHAPE, "%s: N=%d not divisible by groups=%d", who, N, groups);
-    (void)HW;
+    // an empty tensor has no statistics, and its extents would reach FastDiv(0) on the host
+    RPNET_REQUIRE(N >= groups && HW >= 1 && C >= 4, RPNET_ERR_SHAPE, "%s: empty tensor (N=%d HW=%d C=%d)", who, N, HW, C);
     return 0;
 }
 
@@ -835,6 +836,7 @@ extern "C" int rpnet_bn_stats_from_partial(const double* partial, int nblk, int 
     RPNET_REQUIRE(partial && gamma && beta && scale && shift && mean && invstd && nblk > 0, RPNET_ERR_ARG,
                   "bn_stats_from_partial: null pointer");
     RPNET_REQUIRE(groups >= 1 && N % groups == 0, RPNET_ERR_SHAPE, "bn_stats_from_partial: N=%d groups=%d", N, groups);
+    RPNET_REQUIRE(N >= groups && HW >= 1 && C >= 1, RPNET_ERR_SHAPE, "bn_stats_from_partial: empty tensor (N=%d HW=%d C=%d)", N, HW, C);
     const long R = (long)(N / groups) * HW;
     hipLaunchKernelGGL(bn_stats_finalize, dim3(C), dim3(256), 0, (hipStream_t)stream, partial, nblk, R, C, groups, gamma,
                        beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean, invstd);
@@ -846,6 +848,7 @@ extern "C" int rpnet_bn_eval_affine(const float* gamma, const float* beta, const
                                     rpnet_stream_t stream) {
     using namespace rpnet;
     RPNET_REQUIRE(gamma && beta && running_mean && running_var && scale && shift, RPNET_ERR_ARG, "bn_eval_affine: null pointer");
+    RPNET_REQUIRE(C >= 1, RPNET_ERR_SHAPE, "bn_eval_affine: C=%d", C);
     hipLaunchKernelGGL(bn_eval_affine_kernel, dim3(cdiv(C, 128)), dim3(128), 0, (hipStream_t)stream, gamma, beta,
                        running_mean, running_var, eps, scale, shift, C);
     return check_launch("bn_eval_affine");
@@ -865,7 +868,7 @@ extern "C" int rpnet_bn_relu(const float* y, const float* scale, const float* sh
         RPNET_REQUIRE(planes == 3 || (gamma && beta && split_scale), RPNET_ERR_ARG, "bn_relu: fp16 planes (1 or 2) need gamma, beta and the scale output");
         const PoolGeom pg = make_pool_geom(HW, pool_w, N, groups, C);
         const size_t total8 = (size_t)N * (HW / 4) * C / 8, pe = (size_t)N * (HW / 4) * C;
-        RPNET_REQUIRE(total8 < kIndex32, RPNET_ERR_SHAPE, "bn (pooled): %zu elements do not fit the 32-bit index arithmetic of the passes", total8);
+        RPNET_REQUIRE(total8 < kIndex32, RPNET_ERR_SHAPE, "bn_relu: (pooled) %zu elements do not fit the 32-bit index arithmetic of the passes", total8);
         const float sqrt_n = sqrtf((float)((size_t)(N / groups) * HW)) * 1.0001f;
         // the guards of the pooled passes (see bn_bwd_apply_pool_split): LDS reservation of the launch, full wait in the kernel
         const size_t alone_f = pool_alone_bytes();
@@ -882,7 +885,7 @@ extern "C" int rpnet_bn_relu(const float* y, const float* scale, const float* sh
         return check_launch("bn_relu_pool");
     }
     const size_t total4 = (size_t)N * HW * C / 4, group4 = total4 / groups;
-    RPNET_REQUIRE(total4 < kIndex32, RPNET_ERR_SHAPE, "bn: %zu 16-byte elements do not fit the 32-bit index arithmetic of the passes", total4);
+    RPNET_REQUIRE(total4 < kIndex32, RPNET_ERR_SHAPE, "bn_relu: %zu 16-byte elements do not fit the 32-bit index arithmetic of the passes", total4);
     if (z_split) {
         RPNET_REQUIRE(planes >= 1 && planes <= 3 && C % 8 == 0, RPNET_ERR_SHAPE, "bn_relu: split planes=%d C=%d", planes, C);
         const size_t total8 = total4 / 2, pe = (size_t)N * HW * C;
@@ -946,6 +949,9 @@ extern "C" int rpnet_bn_bwd(const float* dz, const float* y, const float* gamma,
         // again from y; dy comes out at full resolution
         RPNET_REQUIRE(dy_split && !given_partial, RPNET_ERR_ARG, "bn_bwd: the pooled form writes split planes and runs its own reduction");
         RPNET_REQUIRE(HW % pool_w == 0 && pool_w % 2 == 0 && (HW / pool_w) % 2 == 0, RPNET_ERR_SHAPE, "bn_bwd: pooled image %d x %d", HW / pool_w, pool_w);
+        const size_t total8 = (size_t)N * (HW / 4) * C / 8, pe = (size_t)N * HW * C;
+        // (in front of every launch: a refused call has run nothing)
+        RPNET_REQUIRE(total8 < kIndex32, RPNET_ERR_SHAPE, "bn_bwd: (pooled) %zu elements do not fit the 32-bit index arithmetic of the passes", total8);
         const PoolGeom pg = make_pool_geom(HW, pool_w, N, groups, C);
         const long Rp = R / 4;
         const BnGeom gp = bn_geom(Rp, C);
@@ -960,8 +966,6 @@ extern "C" int rpnet_bn_bwd(const float* dz, const float* y, const float* gamma,
                                pmax, Rp, C, gp, pg);
         hipLaunchKernelGGL(bn_bwd_finalize, dim3(C), dim3(256), 0, s, (const double*)partial, gp.nblk, R, C, groups,
                            coef, dgamma, dbeta, accumulate, (const float*)pmax, scale, bound);
-        const size_t total8 = (size_t)N * (HW / 4) * C / 8, pe = (size_t)N * HW * C;
-        RPNET_REQUIRE(total8 < kIndex32, RPNET_ERR_SHAPE, "bn (pooled): %zu elements do not fit the 32-bit index arithmetic of the passes", total8);
         // DRAIN (default; RPNET_BN_POOL_DRAIN=0: the A/B switch that brings the fault back): see bn_bwd_apply_pool_split
         static const bool drain = [] { const char* e = getenv("RPNET_BN_POOL_DRAIN"); return !(e && e[0] == '0'); }();
 #define RPNET_BN_POOL_BWD(NP_)                                                                                              \
@@ -975,6 +979,11 @@ extern "C" int rpnet_bn_bwd(const float* dz, const float* y, const float* gamma,
 #undef RPNET_BN_POOL_BWD
         return check_launch("bn_bwd_pool");
     }
+    const size_t total4 = (size_t)N * HW * C / 4, group4 = total4 / groups;
+    // The limit of the APPLY passes (their FastDiv index arithmetic is 32-bit), in front of the reduction's launches: a refused call
+    // has run nothing.  The reduction-only call (dy == dy_split == NULL) is exempt on purpose: bn_bwd_partial and the finalize index
+    // with long / size_t.  rpnet_bn_eval_bwd follows the same rule.
+    RPNET_REQUIRE((!dy && !dy_split) || total4 < kIndex32, RPNET_ERR_SHAPE, "bn_bwd: %zu 16-byte elements do not fit the 32-bit index arithmetic of the passes", total4);
     if (given_partial) {
         // the caller made the sums itself (the first layer without its pre-BatchNorm tensor: rpnet_conv1_bn_bwd_partial):
         // [groups * given_rows][C][2] sums (and [..][C] maxima for fp16 planes)
@@ -994,8 +1003,6 @@ extern "C" int rpnet_bn_bwd(const float* dz, const float* y, const float* gamma,
     // dy == NULL and dy_split == NULL: reduction pass only — dgamma, dbeta and the coefficients (workspace +
     // rpnet_bn_bwd_coef_offset) for a consumer that forms dy itself (rpnet_conv1_wgrad_bn)
     if (!dy && !dy_split) return check_launch("bn_bwd");
-    const size_t total4 = (size_t)N * HW * C / 4, group4 = total4 / groups;
-    RPNET_REQUIRE(total4 < kIndex32, RPNET_ERR_SHAPE, "bn: %zu 16-byte elements do not fit the 32-bit index arithmetic of the passes", total4);
     if (dy_split) {
         const size_t total8 = total4 / 2, pe = (size_t)N * HW * C;
         if (planes == 3)
@@ -1044,7 +1051,8 @@ extern "C" int rpnet_bn_eval_bwd(const float* dz, const float* y, const float* s
     RPNET_REQUIRE(workspace_bytes >= rpnet_bn_workspace_bytes(C, groups), RPNET_ERR_WORKSPACE, "bn_eval_bwd: workspace too small");
     const long R = (long)(N / groups) * HW;
     const size_t total4 = (size_t)N * HW * C / 4, group4 = total4 / groups;
-    RPNET_REQUIRE(total4 < kIndex32, RPNET_ERR_SHAPE, "bn: %zu 16-byte elements do not fit the 32-bit index arithmetic of the passes", total4);
+    // (the apply passes' limit, as in rpnet_bn_bwd: the reduction-only call runs no 32-bit index arithmetic and is exempt)
+    RPNET_REQUIRE((!dy && !dy_split) || total4 < kIndex32, RPNET_ERR_SHAPE, "bn_eval_bwd: %zu 16-byte elements do not fit the 32-bit index arithmetic of the passes", total4);
     const BnGeom gm = bn_geom(R, C);
     hipStream_t s = (hipStream_t)stream;
     double* partial = (double*)workspace;

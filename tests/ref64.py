@@ -325,3 +325,93 @@ def bn_dy(dz, y, stats, coef=None, groups=1, dtype=F64):
 def conv1_dgrad(dy, w, dtype=F64):
     """dy [N, H, W, cout], w [cout, 1, 3, 3] -> dx [N, H, W]: the adjoint of conv1 with respect to the image"""
     return F.conv_transpose2d(_c(dy, dtype).permute(0, 3, 1, 2), _c(w, dtype), padding=1)[:, 0]
+
+
+# ------------------------------- BatchNorm2d + ReLU, train and eval mode (net/modules.py:48-52; csrc/bn.hip), NHWC, [groups, C] statistics
+def bn_stats(y, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, groups=1, dtype=F64):
+    """nn.BatchNorm2d in train mode called once per statistic group, in group order, on y [N, H, W, C] (group g = images
+    g N/groups ...): -> (scale, shift, mean, invstd) each [groups, C] with scale = gamma invstd, shift = beta - mean scale, and the
+    running buffers after one momentum update per group with the UNBIASED variance (None stays None)"""
+    y, gamma, beta = _c(y, dtype), _c(gamma, dtype), _c(beta, dtype)
+    yg = y.reshape(groups, -1, y.shape[-1])
+    R = yg.shape[1]
+    mean, var = yg.mean(1), yg.var(1, unbiased=False)
+    invstd = (var + eps).rsqrt()
+    scale = gamma[None] * invstd
+    rm, rv = _c(running_mean, dtype), _c(running_var, dtype)
+    for g in range(groups):
+        if rm is not None:
+            rm = (1 - momentum) * rm + momentum * mean[g]
+        if rv is not None:
+            rv = (1 - momentum) * rv + momentum * (var[g] * R / (R - 1) if R > 1 else var[g])
+    return scale, beta[None] - mean * scale, mean, invstd, rm, rv
+
+
+def bn_relu(y, scale, shift, groups=1, dtype=F64):
+    """z = relu(y scale[g] + shift[g]) [N, H, W, C]"""
+    return conv1_affine_relu(y, scale, shift, groups, dtype)
+
+
+def bn_relu_pool(y, scale, shift, groups=1, dtype=F64):
+    """max_pool2d(2, 2) of bn_relu -> [N, H/2, W/2, C]"""
+    return maxpool2(bn_relu(y, scale, shift, groups, dtype), dtype)
+
+
+def _pinned(value, fn):
+    """`value` (a constant) with the gradient of fn: the statistic at the value the caller was given"""
+    return value + (fn - fn.detach())
+
+
+def bn_bwd(dz, y, stats, groups=1, pooled=False, dtype=F64):
+    """autograd of the train-mode expression z = relu(gamma xhat(y) + beta) (pooled: max_pool2d(z, 2, 2), dz the pooled gradient;
+    torch routes a window's gradient to its first maximum in row, column scan order), the batch mean and invstd held at the VALUES
+    of stats [4][groups][C] (scale, shift, mean, invstd: what the kernels are given) while their gradients are those of the batch
+    statistics.  -> (dy [N, H, W, C], dgamma [C], dbeta [C] summed over groups, coef [groups, C, 2] = (sum dz m, sum dz m xhat) / R)"""
+    st = _c(stats, dtype).reshape(4, groups, -1)
+    y = _c(y, dtype).clone().requires_grad_(True)
+    N, C = y.shape[0], y.shape[-1]
+    sc, sh, mu, inv = st
+    gamma = [(sc[g] / inv[g]).clone().requires_grad_(True) for g in range(groups)]
+    beta = [(sh[g] + mu[g] * sc[g]).clone().requires_grad_(True) for g in range(groups)]
+    zs, xh = [], []
+    for g in range(groups):
+        yg = y[g * (N // groups):(g + 1) * (N // groups)]
+        m = _pinned(mu[g], yg.mean((0, 1, 2)))
+        d = yg - m
+        v = (d * d).mean((0, 1, 2))
+        istd = _pinned(inv[g], (v + (inv[g] ** -2 - v.detach())).rsqrt())
+        xh.append(d * istd)
+        zs.append(torch.relu(xh[-1] * gamma[g] + beta[g]))
+    z = torch.cat(zs)
+    if pooled:
+        z = _nhwc(F.max_pool2d(z.permute(0, 3, 1, 2), 2, 2))
+    grads = torch.autograd.grad(z, [y] + gamma + beta, _c(dz, dtype))
+    dy, dgs, dbs = grads[0], torch.stack(grads[1:1 + groups]), torch.stack(grads[1 + groups:])
+    R = y[0].numel() // C * (N // groups)
+    return dy, dgs.sum(0), dbs.sum(0), torch.stack([dbs, dgs], -1) / R
+
+
+def bn_eval_affine(gamma, beta, running_mean, running_var, eps=1e-5, dtype=F64):
+    """-> (scale, shift) [C] of eval-mode BatchNorm: gamma / sqrt(running_var + eps), beta - running_mean scale"""
+    scale = _c(gamma, dtype) / (_c(running_var, dtype) + eps).sqrt()
+    return scale, _c(beta, dtype) - _c(running_mean, dtype) * scale
+
+
+def bn_eval_relu(y, scale, shift, dtype=F64):
+    """y [P, C] -> (z = relu(y scale + shift), max z: the running absmax starts at 0)"""
+    z = torch.relu(_c(y, dtype) * _c(scale, dtype) + _c(shift, dtype))
+    return z, z.max().clamp_min(0) if z.numel() else torch.zeros((), dtype=dtype)
+
+
+def bn_eval_bwd(dz, y, stats, groups=1, dtype=F64):
+    """autograd of z = relu(gamma (y - mean) invstd + beta) with CONSTANT statistics (stats [4][groups][C], group g's rows of it
+    for the images of group g) -> (dy, dgamma [C], dbeta [C] summed over groups)"""
+    st = _c(stats, dtype).reshape(4, groups, -1)
+    y = _c(y, dtype).clone().requires_grad_(True)
+    N = y.shape[0]
+    sc, sh, mu, inv = st
+    gamma = (sc / inv).clone().requires_grad_(True)
+    beta = (sh + mu * sc).clone().requires_grad_(True)
+    z = torch.relu((y - _per_image(mu, N)) * _per_image(inv, N) * _per_image(gamma, N) + _per_image(beta, N))
+    dy, dg, db = torch.autograd.grad(z, (y, gamma, beta), _c(dz, dtype))
+    return dy, dg.sum(0), db.sum(0)
