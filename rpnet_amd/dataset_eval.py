@@ -99,9 +99,10 @@ def ncc_pairs(query, warped, affine, table, row):
 class DeviceEvalSource:
     """config: the keys of FewshotVolumeReader / FewshotSliceReader (class_csv_dir, eval_classes, k, do_deformable, crop_size, ...);
     one way, one shot (`test_shot` 1), `use_registration_loss: True` and no `use_registration_mask` (what tools/eval_driver.py runs).
-    cache_volumes=False reloads a volume every time it is used.  `k` sticks across items, as in the host reader."""
+    cache_volumes=False reloads a volume every time it is used.  device_load=True builds a volume on the device from the payloads of its
+    files (rpnet_amd.volume_load.DeviceVolumeLoader), the same bits as the host reader's.  `k` sticks across items, as in the host reader."""
 
-    def __init__(self, data_dir, set_name, config, device, cache_volumes=True):
+    def __init__(self, data_dir, set_name, config, device, cache_volumes=True, device_load=False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceEvalSource runs on MI355X only (there is no CPU fallback; the host reader is "
@@ -119,17 +120,31 @@ class DeviceEvalSource:
         self.cfg, self.k = config, config["k"]
         self.reader = FewshotVolumeReader(data_dir, set_name, config, mode="eval")
         self.cache_volumes, self._volumes = cache_volumes, {}
+        self.loader = None
+        self.set_device_load(device_load)
         self.pre = None               # the last item's gathered tensors before registration and its slice table
 
     def __len__(self):
         return len(self.reader)
 
+    def set_device_load(self, on):
+        """volumes loaded from here on come from the device loader (True) or from the host reader (False); cached volumes stay, they
+        hold the same bits either way"""
+        if on and self.loader is None:
+            from .volume_load import DeviceVolumeLoader
+            self.loader = DeviceVolumeLoader(self.reader, self.device)
+        elif not on:
+            self.loader = None
+
     def volume(self, c, i):
         """(image [D,H,W], mask [D,H,W]) float32 on the device: the reader's deterministic preprocessing, once"""
         if (c, i) in self._volumes:
             return self._volumes[(c, i)]
-        s = self.reader.load_image_and_mask(self.reader.data_info[c][i]["pid"], self.reader.classes[c])
-        v = (torch.from_numpy(s["image"][0]).to(self.device), torch.from_numpy(s["mask"][0]).to(self.device))
+        if self.loader is not None:
+            v = self.loader.load(self.reader.data_info[c][i]["pid"], self.reader.classes[c])
+        else:
+            s = self.reader.load_image_and_mask(self.reader.data_info[c][i]["pid"], self.reader.classes[c])
+            v = (torch.from_numpy(s["image"][0]).to(self.device), torch.from_numpy(s["mask"][0]).to(self.device))
         if self.cache_volumes:
             self._volumes[(c, i)] = v
         return v
@@ -182,7 +197,7 @@ def item_spacings(source, n, spacing):
 
 def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False,
                      spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None, min_component=None,
-                     opening=None, closing=None, morph_per_slice=False):
+                     opening=None, closing=None, morph_per_slice=False, device_load=None):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -217,9 +232,13 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     becomes open -> remove small -> keep largest -> close -> fill holes.  One more device table, int64 [n_items, K-1, 8] (columns 0..3
     the statistics row of the opening, 4..7 that of the closing, zeros for a stage that is off), is fetched once per data set and
     arrives as out["morph_stats"]; every item line gains ` open -<removed> +<added>` and ` close -<removed> +<added>` for the stages
-    that are on, after the figures above, every class line their means.  With both None nothing changes."""
+    that are on, after the figures above, every class line their means.  With both None nothing changes.
+    device_load (None: as the source was built; True / False): the source's volumes are built on the device from the payloads of their
+    files (DeviceEvalSource.set_device_load); the tables and lines are the same either way."""
     from .utils import nrrd
     from .volume import check_min_component
+    if device_load is not None:
+        source.set_device_load(bool(device_load))
     conn = CC.connectivity_of(keep_largest)
     holes_on, small_min = PP.holes_mode_of(fill_holes) is not None, check_min_component(min_component)
     small_on = small_min is not None

@@ -24,12 +24,14 @@ class DeviceEpisodeSource:
     """config: the keys of FewshotVolumeReader / FewshotSliceReader (class_csv_dir, train_classes, k, do_elastic,
     do_intaug, gamma_range, do_deformable, crop_size, ...); one way, one shot, `use_registration_loss: True` (what
     FewshotRegReader needs).  `elastic_random_state`: the RandomState of the elastic draws (None: unseeded, as the
-    host reader's).  cache_volumes=False reloads a volume every time it is used.  rank / world: batch() starts at item
+    host reader's).  cache_volumes=False reloads a volume every time it is used.  device_load=True builds a volume on the device from
+    the payloads of its files (rpnet_amd.volume_load.DeviceVolumeLoader), the same bits as the host reader's.  rank / world: batch() starts at item
     `rank` and strides by `world`, so that the processes of a data-parallel run walk different query volumes."""
 
     FIELDS = ("support_images", "support_labels", "query_images", "query_labels", "appr_query_labels")
 
-    def __init__(self, data_dir, set_name, config, device, cache_volumes=True, elastic_random_state=None, rank=0, world=1):
+    def __init__(self, data_dir, set_name, config, device, cache_volumes=True, elastic_random_state=None, rank=0, world=1,
+                 device_load=False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceEpisodeSource runs on MI355X only (there is no CPU fallback; the host reader is "
@@ -41,6 +43,10 @@ class DeviceEpisodeSource:
         self.cfg, self.k = config, config["k"]
         self.reader = FewshotVolumeReader(data_dir, set_name, config, mode="train")
         self.cache_volumes, self._volumes = cache_volumes, {}
+        self.loader = None
+        if device_load:
+            from .volume_load import DeviceVolumeLoader
+            self.loader = DeviceVolumeLoader(self.reader, self.device)
         self.elastic_random_state = elastic_random_state
         self.pre = None               # the last item's tensors before registration, its slice picks and parameter table
         self.last_elastic = None      # the last item's (Minv, noise), None when the coin fell the other way
@@ -54,8 +60,11 @@ class DeviceEpisodeSource:
         """(image [D,H,W], mask [D,H,W]) float32 on the device: the reader's deterministic preprocessing, once"""
         if (c, i) in self._volumes:
             return self._volumes[(c, i)]
-        s = self.reader.load_image_and_mask(self.reader.data_info[c][i]["pid"], self.reader.classes[c])
-        v = (torch.from_numpy(s["image"][0]).to(self.device), torch.from_numpy(s["mask"][0]).to(self.device))
+        if self.loader is not None:
+            v = self.loader.load(self.reader.data_info[c][i]["pid"], self.reader.classes[c])
+        else:
+            s = self.reader.load_image_and_mask(self.reader.data_info[c][i]["pid"], self.reader.classes[c])
+            v = (torch.from_numpy(s["image"][0]).to(self.device), torch.from_numpy(s["mask"][0]).to(self.device))
         if self.cache_volumes:
             self._volumes[(c, i)] = v
         return v

@@ -283,6 +283,25 @@ SIDE_ABIS_AFTER_RESAMPLE = [
     ("rpnet_smooth_abi.h", "smoothing", "rpnet_smooth_abi_version", SMOOTH_ABI_VERSION, _SMOOTH_SIGS),
 ]
 
+# the reader's preprocessing of a volume from the payload of its file (annotated z range, gather, rank selection, clip and map):
+# include/rpnet_volload_abi.h (ledger: tests/volload_abi_ledger.py).  The twelfth side family.  tests/test_host_smooth_abi_ledger.py holds
+# SIDE_ABIS_AFTER_RESAMPLE to the one row above, so this family stands in a further table of the same form; load() binds and checks
+# ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH.
+_VOLLOAD_SOURCE = [vp, ci, ci, ci, ci, ci, ci, ci, ci]      # source, kind, layout, D, H, W, num_slice, num_y, num_x
+_VOLLOAD_SIGS = {
+    "rpnet_volload_abi_version": (ci, []),
+    "rpnet_volload_select_workspace_bytes": (cs, [cs]),
+    "rpnet_volload_range": (ci, _VOLLOAD_SOURCE + [vp, vp]),
+    "rpnet_volload_gather": (ci, _VOLLOAD_SOURCE + [ci, ci, ci, ci, cf, vp, vp]),
+    "rpnet_volload_select": (ci, [vp, cs, cs, cs, vp, vp, cs, vp]),
+    "rpnet_volload_normalize": (ci, [vp, vp, cs, vp, cf, cf, cf, cf, vp]),
+}
+VOLLOAD_ABI_SYMBOLS = tuple(_VOLLOAD_SIGS)
+VOLLOAD_ABI_VERSION = 1     # RPNET_VOLLOAD_ABI_VERSION of include/rpnet_volload_abi.h
+SIDE_ABIS_AFTER_SMOOTH = [
+    ("rpnet_volload_abi.h", "volume-loading", "rpnet_volload_abi_version", VOLLOAD_ABI_VERSION, _VOLLOAD_SIGS),
+]
+
 
 def lib_path():
     return _LIB_PATH
@@ -300,7 +319,7 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE
+        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH
         for sigs in [_SIGS] + [family[4] for family in side_abis]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)

@@ -245,6 +245,9 @@ def build_parser():
     ap.add_argument("--save-pred", default=None, metavar="DIR", help="write each volume's mask as DIR/<pid>_<class>.nrrd; implies --on-device")
     ap.add_argument("--device-items", action="store_true",
                     help="build the items on the device too and fetch all tallies once (rpnet_amd.dataset_eval); implies --on-device")
+    ap.add_argument("--device-load", action="store_true",
+                    help="with --device-items: crop, percentile clip and normalise every volume on the device from the payloads of its "
+                         "files (rpnet_amd.volume_load), the same bits as the host reader's")
     ap.add_argument("--surface", action="store_true",
                     help="HD95 and ASSD of the final mask and the affine baseline at the end of every line (rpnet_amd.surface); implies --on-device")
     ap.add_argument("--keep-largest", type=int, nargs="?", const=6, default=0, choices=(6, 26), metavar="6|26",
@@ -280,6 +283,8 @@ def main():
     spacing = parse_spacing(a.spacing if a.spacing is not None else config.get("surface_spacing"))
     tolerance = a.surface_tolerance if a.surface_tolerance is not None else config.get("surface_tolerance")
     a.surface = a.surface or spacing is not None or tolerance is not None
+    if a.device_load and not a.device_items:
+        raise SystemExit("--device-load needs --device-items")
     min_component = parse_min_component(a.min_component)
     if a.max_hole is not None and a.fill_holes is None:
         raise SystemExit("--max-hole needs --fill-holes")
@@ -302,7 +307,7 @@ def main():
         net.load_state_dict(state)
     if a.device_items:
         from rpnet_amd.dataset_eval import DeviceEvalSource, evaluate_dataset
-        source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device)
+        source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device, device_load=a.device_load)
         source.warm()
         evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface,
                          keep_largest=a.keep_largest or False, spacing=spacing, surface_tolerance=tolerance, **post)

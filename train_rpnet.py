@@ -170,9 +170,13 @@ def main():
                     "clip_grad_norm; absent: off).  fused: inside the step, on the device; torch: torch.nn.utils.clip_grad_norm_")
     ap.add_argument("--skip_nonfinite", action="store_true", help="do not take a step whose gradient holds an inf or a NaN (yaml "
                     "key skip_nonfinite; absent: off).  Needs --optimizer fused")
+    ap.add_argument("--device_load", action="store_true", help="with --data_dir: crop, percentile clip and normalise every volume on the "
+                    "device from the payloads of its files (rpnet_amd.volume_load), the same bits as the host reader's")
     a = ap.parse_args()
     if (a.data_dir is None) != (a.set_name is None):
         ap.error("--data_dir and --set_name come together")
+    if a.device_load and a.data_dir is None:
+        ap.error("--device_load needs --data_dir")
     config, _ = load_yaml(a.yaml)
     clip_grad_norm = a.clip_grad_norm if a.clip_grad_norm is not None else config.get("clip_grad_norm")
     skip_nonfinite = a.skip_nonfinite or bool(config.get("skip_nonfinite", False))
@@ -204,7 +208,8 @@ def main():
     source = None
     if a.data_dir is not None:
         from rpnet_amd.episodes import DeviceEpisodeSource
-        source = DeviceEpisodeSource(a.data_dir, a.set_name, config, dev, rank=int(os.environ.get("RANK", "0")), world=world)
+        source = DeviceEpisodeSource(a.data_dir, a.set_name, config, dev, rank=int(os.environ.get("RANK", "0")), world=world,
+                                     device_load=a.device_load)
     train(config, a.steps, a.batch or config["batch_size"], a.size, dev, lr=a.lr, out_dir=a.out_dir or config.get("out_dir"),
           source=source, optimizer=a.optimizer, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
     if world > 1:
