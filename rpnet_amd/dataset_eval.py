@@ -151,11 +151,13 @@ class DeviceEvalSource:
 
     def warm(self):
         """load every volume and the small constants of the registration (its base grids and, with do_deformable, its smoothing
-        kernel), so that no later item copies anything up with a blocking copy"""
+        kernel, or the DEEDS base grids with do_deformable "deeds"), so that no later item copies anything up with a blocking copy"""
         for c, i in self.reader.indices:
             img = self.volume(c, i)[0]
             R.base_grid(img.shape[2], img.device), R.base_grid(img.shape[1], img.device)
-            if self.cfg.get("do_deformable", True):
+            if self.cfg.get("do_deformable", True) == "deeds":
+                R.base_grid(128, img.device), R.base_grid(15, img.device)       # the keys deeds_register and deeds_warp look up
+            elif self.cfg.get("do_deformable", True):
                 R._device_kernel((2.0, 2.0), img.device)            # the key demons_register looks up
 
     def item(self, idx):

@@ -302,6 +302,23 @@ SIDE_ABIS_AFTER_SMOOTH = [
     ("rpnet_volload_abi.h", "volume-loading", "rpnet_volload_abi_version", VOLLOAD_ABI_VERSION, _VOLLOAD_SIGS),
 ]
 
+# DEEDS registration of the reader's slices (cost volume in LDS, softmax expectation, warp by the upsampled grid):
+# include/rpnet_deeds_abi.h (ledger: tests/deeds_abi_ledger.py).  The thirteenth side family.  tests/test_host_volload_abi_ledger.py holds
+# SIDE_ABIS_AFTER_SMOOTH to the one row above, so this family stands in a further table of the same form; load() binds and checks
+# ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD.
+_DEEDS_SIGS = {
+    "rpnet_deeds_abi_version": (ci, []),
+    "rpnet_deeds_workspace_bytes": (cs, [ci, ci, ci, ci]),
+    # moving, fixed, gbase, sbase, S, H, W, G, D, disp_range, alpha0..5, pred, cost_out, ws, ws_bytes, stream
+    "rpnet_deeds_register": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, cf, cf, cf, vp, vp, vp, cs, vp]),
+    "rpnet_deeds_warp": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, vp]),
+}
+DEEDS_ABI_SYMBOLS = tuple(_DEEDS_SIGS)
+DEEDS_ABI_VERSION = 1     # RPNET_DEEDS_ABI_VERSION of include/rpnet_deeds_abi.h
+SIDE_ABIS_AFTER_VOLLOAD = [
+    ("rpnet_deeds_abi.h", "DEEDS-registration", "rpnet_deeds_abi_version", DEEDS_ABI_VERSION, _DEEDS_SIGS),
+]
+
 
 def lib_path():
     return _LIB_PATH
@@ -319,7 +336,7 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH
+        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD
         for sigs in [_SIGS] + [family[4] for family in side_abis]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)

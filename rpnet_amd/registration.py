@@ -3,7 +3,9 @@ net/registration.py:316-357,474-502), batched over the slices of a volume.  Affi
 shipped configuration `do_deformable: False`, yamls/example.yml:99-101): ONE kernel launch registers all slices
 (rpnet_affine_register: a block per slice runs the 50 Adam steps on-chip), six more warp them.  Deformable stage
 (`do_deformable: True`, the reader's default when the key is absent): rpnet_demons_register advances the dense flow
-fields of all slices together, 24 launches per Adam step enqueued from C (csrc/demons.hip).
+fields of all slices together, 24 launches per Adam step enqueued from C (csrc/demons.hip).  DEEDS stage
+(`do_deformable: deeds`, net/registration.py:360-381,412-471,505-518): rpnet_deeds_register builds and regularises the cost
+volume of all slices in ONE launch, in LDS, and takes the softmax expectation of the displacements (csrc/deeds.hip).
 
 The reference does this slice by slice with ~20 small torch operators per Adam step — on the CPU in this
 configuration (few_shot_reader.py:135-143) — and it dominates the wall-clock of real evaluation outside the
@@ -97,13 +99,64 @@ def displacement_warp(x, disp, threshold=-1.0, scale=1.0, shift=0.0):
     return out
 
 
+DEEDS_ALPHA = (1, .1, 1, 0, .1, 10)      # DEEDSRegistration.alpha (net/registration.py:369)
+DEEDS_MODES = {"nearest": 0, "bilinear": 1}     # RPNET_DEEDS_NEAREST, RPNET_DEEDS_BILINEAR
+# the values of the yaml key do_deformable by the names the drivers' --registration takes
+REGISTRATION_STAGES = {"affine": False, "demons": True, "deeds": "deeds"}
+
+
+def deeds_register(moving, fixed, grid_size=128, disp_range=0.1, displacement_width=15, alpha=DEEDS_ALPHA, return_cost=False):
+    """DEEDSRegistration.train_registraion (net/registration.py:412-466) for all slices at once: moving, fixed [S,H,W] fp32 on the
+    GPU -> pred [S,G,G,2], the expected (x, y) displacement of every grid point in normalised coordinates; with return_cost also the
+    regularised cost [S,G*G,D*D] that enters the softmax.  One launch with alpha[3] == 0 (csrc/deeds.hip)."""
+    hip.require_gpu(moving, fixed)
+    S, H, W = moving.shape
+    G, D = int(grid_size), int(displacement_width)
+    alpha = [float(a) for a in alpha]
+    if len(alpha) != 6:
+        raise ValueError("deeds_register: alpha has six values")
+    if not (1 <= G <= 512 and 1 <= D <= 31 and D % 2 == 1):
+        raise ValueError(f"deeds_register: grid_size={G} (1..512), displacement_width={D} (odd, 1..31)")
+    pred = torch.empty((S, G, G, 2), device=moving.device, dtype=torch.float32)
+    cost = torch.empty((S, G * G, D * D), device=moving.device, dtype=torch.float32) if return_cost else None
+    wb = hip.query("rpnet_deeds_workspace_bytes", S, G, D, int(alpha[3] != 0.0))
+    ws = torch.empty((wb,), device=moving.device, dtype=torch.uint8) if wb else None
+    gbase, sbase = base_grid(G, moving.device), base_grid(D, moving.device)
+    call("rpnet_deeds_register", ptr(moving.contiguous()), ptr(fixed.contiguous()), ptr(gbase), ptr(sbase), S, H, W, G, D,
+         float(disp_range), *alpha, ptr(pred), ptr(cost), ptr(ws), wb)
+    return (pred, cost) if return_cost else pred
+
+
+def deeds_warp(x, pred, mode="nearest", threshold=-1.0, scale=1.0, shift=0.0):
+    """DEEDSRegistration.forward (net/registration.py:377-381,466-471): x [S,H,W] sampled at (grid + pred) brought to H x W by
+    F.upsample(mode) -> [threshold](scale * warped + shift)."""
+    hip.require_gpu(x, pred)
+    S, H, W = x.shape
+    G = pred.shape[1]
+    if mode not in DEEDS_MODES:
+        raise ValueError(f"deeds_warp: mode {mode!r} (one of {sorted(DEEDS_MODES)})")
+    out = torch.empty_like(x)
+    call("rpnet_deeds_warp", ptr(x.contiguous()), ptr(pred.contiguous()), ptr(base_grid(G, x.device)), ptr(out), S, H, W, G,
+         DEEDS_MODES[mode], threshold, scale, shift)
+    return out
+
+
 def register_slices(src, dst, lab, do_deformable=True):
     """The registration pre-step on device tensors: src (support), dst (query) [S,H,W] in [0,1], lab [S,H,W], float32 on
     the GPU -> (field, reg_pred [S,H,W], warped_src [S,H,W], affine_reg_pred [S,H,W], affine_warped_src [S,H,W]), all
-    on the GPU, nothing copied to the host; field = theta [S,2,3], or (theta, flow [S,2,H,W]) with do_deformable."""
+    on the GPU, nothing copied to the host; field = theta [S,2,3], or (theta, flow [S,2,H,W]) with do_deformable, or
+    (theta, pred [S,G,G,2]) with do_deformable="deeds"."""
     theta, _ = affine_register(src, dst)
     aw_lab, aw_src = affine_warp(lab, theta), affine_warp(src, theta)
-    if do_deformable:
+    if isinstance(do_deformable, str):
+        # AffineDEEDSRegistration (net/registration.py:505-518): one DEEDS pass on the affine-warped source
+        if do_deformable != "deeds":
+            raise ValueError(f"register_slices: do_deformable {do_deformable!r} (True, False or 'deeds')")
+        pred = deeds_register(aw_src, dst)
+        field = (theta, pred)
+        reg_pred = deeds_warp(aw_lab, pred, threshold=0.1)
+        warped_src = deeds_warp(aw_src, pred, scale=2.0, shift=-1.0)
+    elif do_deformable:
         # few_shot_reader.py:135-143,152-161: 50 demons steps on the affine-warped source (net/registration.py:489-502)
         flow, disp, _ = demons_register(aw_src, dst)
         field = (theta, flow)

@@ -273,12 +273,17 @@ def build_parser():
                     help="close the final mask by a ball of this radius in voxels, or in millimetres under --spacing, before the holes are "
                          "filled; implies --on-device")
     ap.add_argument("--morph-slice", action="store_true", help="--opening and --closing on every slice on its own")
+    ap.add_argument("--registration", choices=("affine", "demons", "deeds"), default=None,
+                    help="the registration pre-step of every item (overrides the yaml key do_deformable: False, True or deeds)")
     return ap
 
 
 def main():
     a = build_parser().parse_args()
     config, args = load_yaml(a.yaml)
+    if a.registration is not None:
+        from rpnet_amd.registration import REGISTRATION_STAGES
+        config["do_deformable"] = REGISTRATION_STAGES[a.registration]
     config["n_iter_refinement"] = config["n_test_iter_refinement"]            # test_rpnet.py:51
     spacing = parse_spacing(a.spacing if a.spacing is not None else config.get("surface_spacing"))
     tolerance = a.surface_tolerance if a.surface_tolerance is not None else config.get("surface_tolerance")

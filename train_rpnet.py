@@ -172,12 +172,17 @@ def main():
                     "key skip_nonfinite; absent: off).  Needs --optimizer fused")
     ap.add_argument("--device_load", action="store_true", help="with --data_dir: crop, percentile clip and normalise every volume on the "
                     "device from the payloads of its files (rpnet_amd.volume_load), the same bits as the host reader's")
+    ap.add_argument("--registration", choices=("affine", "demons", "deeds"), default=None, help="with --data_dir: the registration "
+                    "pre-step of every episode (overrides the yaml key do_deformable: False, True or deeds)")
     a = ap.parse_args()
     if (a.data_dir is None) != (a.set_name is None):
         ap.error("--data_dir and --set_name come together")
     if a.device_load and a.data_dir is None:
         ap.error("--device_load needs --data_dir")
     config, _ = load_yaml(a.yaml)
+    if a.registration is not None:
+        from rpnet_amd.registration import REGISTRATION_STAGES
+        config["do_deformable"] = REGISTRATION_STAGES[a.registration]
     clip_grad_norm = a.clip_grad_norm if a.clip_grad_norm is not None else config.get("clip_grad_norm")
     skip_nonfinite = a.skip_nonfinite or bool(config.get("skip_nonfinite", False))
     if skip_nonfinite and a.optimizer == "torch":
