@@ -160,11 +160,17 @@ class DeviceEvalSource:
             elif self.cfg.get("do_deformable", True):
                 R._device_kernel((2.0, 2.0), img.device)            # the key demons_register looks up
 
-    def item(self, idx):
+    def item(self, idx, support=None):
+        """the item of query `idx`.  support: the index of the support volume inside the query's class instead of the drawn one; the draw
+        is still made and then overridden, as FewshotVolumeReader.__getitem__(idx, supp_idx) does, so host and device stay in step"""
         rd, cfg = self.reader, self.cfg
         c, qv = rd.indices[idx]
         others = [i for i in range(rd.n_data[c]) if i != qv]
         (s,) = random.choices(others, k=1)                      # the one draw of the host item (eval mode has no elastic coin)
+        if support is not None:
+            if isinstance(support, bool) or not isinstance(support, (int, np.integer)) or not 0 <= int(support) < rd.n_data[c]:
+                raise ValueError(f"DeviceEvalSource.item: support is the index of a volume of the class, 0..{rd.n_data[c] - 1}, got {support!r}")
+            s = int(support)
         s_img, s_msk = self.volume(c, s)
         q_img, q_msk = self.volume(c, qv)
         if s_img.shape[1:] != q_img.shape[1:]:
@@ -199,7 +205,7 @@ def item_spacings(source, n, spacing):
 
 def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False,
                      spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None, min_component=None,
-                     opening=None, closing=None, morph_per_slice=False, device_load=None):
+                     opening=None, closing=None, morph_per_slice=False, device_load=None, keep_masks=False):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -236,7 +242,9 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     arrives as out["morph_stats"]; every item line gains ` open -<removed> +<added>` and ` close -<removed> +<added>` for the stages
     that are on, after the figures above, every class line their means.  With both None nothing changes.
     device_load (None: as the source was built; True / False): the source's volumes are built on the device from the payloads of their
-    files (DeviceEvalSource.set_device_load); the tables and lines are the same either way."""
+    files (DeviceEvalSource.set_device_load); the tables and lines are the same either way.
+    keep_masks=True: out["masks"] receives the list of every volume's final mask (uint8 [D,H,W] on the device, the end of the clean-up
+    chain where one is on); nothing else changes."""
     from .utils import nrrd
     from .volume import check_min_component
     if device_load is not None:
@@ -294,8 +302,10 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
                   **extra)
         ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
         meta.append((s["pid"], classes[s["class_id"]]))
-        if save_pred:
+        if save_pred or keep_masks:
             masks.append(res.post["mask"] if chain else res.mask)
+    if keep_masks and out is not None:
+        out["masks"] = masks
     counts, ncc = table.cpu().numpy(), ncc.cpu().numpy()          # the two transfers of the data set
     if out is not None:
         out["counts"], out["ncc"] = counts, ncc

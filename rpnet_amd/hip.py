@@ -319,6 +319,26 @@ SIDE_ABIS_AFTER_VOLLOAD = [
     ("rpnet_deeds_abi.h", "DEEDS-registration", "rpnet_deeds_abi_version", DEEDS_ABI_VERSION, _DEEDS_SIGS),
 ]
 
+# label fusion of the masks several raters gave one volume (patterns and their histogram, the decision table, the fused mask):
+# include/rpnet_fusion_abi.h (ledger: tests/fusion_abi_ledger.py).  The fourteenth side family.  tests/test_host_deeds_abi_ledger.py holds
+# SIDE_ABIS_AFTER_VOLLOAD to the one row above, so this family stands in a further table of the same form; load() binds and checks
+# ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD + SIDE_ABIS_AFTER_DEEDS.
+_FUSION_RATERS = [C.POINTER(vp), ci, ci, ci, ci, ci, ci]        # raters (a host array of device pointers), R, kind, cls, D, H, W
+_FUSION_SIGS = {
+    "rpnet_fusion_abi_version": (ci, []),
+    "rpnet_fusion_workspace_bytes": (cs, [ci, ci, ci, ci]),
+    "rpnet_fusion_patterns": (ci, _FUSION_RATERS + [vp, vp, vp]),
+    # method, min_votes, weights, consensus, max_iter, tol, out, merge, prob, truth, truth_kind, counts, counts_row, stats, rater_f, rater_i,
+    # row, n_rows, workspace, workspace_bytes, stream
+    "rpnet_fusion_fuse": (ci, _FUSION_RATERS + [ci, ci, C.POINTER(cd), ci, ci, cd, vp, ci, vp, vp, ci, vp, C.c_int64, vp, vp, vp, C.c_int64,
+                                                C.c_int64, vp, cs, vp]),
+}
+FUSION_ABI_SYMBOLS = tuple(_FUSION_SIGS)
+FUSION_ABI_VERSION = 1     # RPNET_FUSION_ABI_VERSION of include/rpnet_fusion_abi.h
+SIDE_ABIS_AFTER_DEEDS = [
+    ("rpnet_fusion_abi.h", "label-fusion", "rpnet_fusion_abi_version", FUSION_ABI_VERSION, _FUSION_SIGS),
+]
+
 
 def lib_path():
     return _LIB_PATH
@@ -336,7 +356,8 @@ def load():
         if lib.rpnet_version() != ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
-        side_abis = ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD
+        side_abis = (ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD
+                     + SIDE_ABIS_AFTER_DEEDS)
         for sigs in [_SIGS] + [family[4] for family in side_abis]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)

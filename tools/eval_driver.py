@@ -22,6 +22,10 @@ item line ends with ` lcc <dice> (<n_components> components, <removed> voxels re
 --surface-tolerance MM (both imply --surface; the yaml keys surface_spacing and surface_tolerance are their defaults): the surface
 distances in millimetres on the voxel spacing of every query volume's NRRD header, or on one given spacing (rpnet_amd.surface_spacing),
 each figure followed by `mm`, and with a tolerance the normalised surface Dice ` nsd <fewshot> (<affine>)`.
+--runs R [--fuse vote|staple] [--fuse-all-voxels] (needs --device-items): the evaluation R times over, every run with a freshly drawn
+support volume per query, then the reference's "Average performance" block (test_rpnet.py:112-145; rpnet_amd.fusion.evaluate_runs).
+--fuse fuses every query's R final masks on the device by majority vote or STAPLE and prints the fused Dice beside the runs' own;
+--fuse-all-voxels lets the voxels on which all runs agree take part in STAPLE's EM; --save-pred then writes the fused mask.
 """
 import argparse
 import os
@@ -275,6 +279,12 @@ def build_parser():
     ap.add_argument("--morph-slice", action="store_true", help="--opening and --closing on every slice on its own")
     ap.add_argument("--registration", choices=("affine", "demons", "deeds"), default=None,
                     help="the registration pre-step of every item (overrides the yaml key do_deformable: False, True or deeds)")
+    ap.add_argument("--runs", type=int, default=None, metavar="R",
+                    help="with --device-items: evaluate R times, each run with a freshly drawn support volume per query, and print the "
+                         "average over the runs (rpnet_amd.fusion.evaluate_runs)")
+    ap.add_argument("--fuse", choices=("vote", "staple"), default=None,
+                    help="with --runs: fuse every query's masks of the R runs on the device (rpnet_amd.fusion); --save-pred writes the fused mask")
+    ap.add_argument("--fuse-all-voxels", action="store_true", help="with --fuse staple: the voxels all runs agree on take part in the EM")
     return ap
 
 
@@ -290,6 +300,10 @@ def main():
     a.surface = a.surface or spacing is not None or tolerance is not None
     if a.device_load and not a.device_items:
         raise SystemExit("--device-load needs --device-items")
+    if a.runs is not None and not a.device_items:
+        raise SystemExit("--runs needs --device-items")
+    if (a.fuse or a.fuse_all_voxels) and a.runs is None:
+        raise SystemExit("--fuse and --fuse-all-voxels need --runs")
     min_component = parse_min_component(a.min_component)
     if a.max_hole is not None and a.fill_holes is None:
         raise SystemExit("--max-hole needs --fill-holes")
@@ -314,6 +328,14 @@ def main():
         from rpnet_amd.dataset_eval import DeviceEvalSource, evaluate_dataset
         source = DeviceEvalSource(args.data_dir, args.eval_set_name, config, next(net.parameters()).device, device_load=a.device_load)
         source.warm()
+        if a.runs is not None:
+            from rpnet_amd.fusion import evaluate_runs, save_fused
+            _, _, fused = evaluate_runs(net, source, config, a.runs, a.fuse, not a.fuse_all_voxels, a.items, a.batch or 8,
+                                        save_pred=None if a.fuse else a.save_pred, surface=a.surface, keep_largest=a.keep_largest or False,
+                                        spacing=spacing, surface_tolerance=tolerance, **post)
+            if a.fuse and a.save_pred:
+                save_fused(fused, source, config, a.save_pred)
+            return
         evaluate_dataset(net, source, config, a.items, a.batch or 8, save_pred=a.save_pred, surface=a.surface,
                          keep_largest=a.keep_largest or False, spacing=spacing, surface_tolerance=tolerance, **post)
     elif a.on_device or a.save_pred or a.surface or a.keep_largest or a.fill_holes or min_component is not None or "opening" in post:
