@@ -24,6 +24,7 @@ from . import components as CC
 from . import morphology as MO
 from . import postprocess as PP
 from . import hip
+from . import regions as RG
 from . import registration as R
 from . import surface as SF
 from . import surface_spacing as SS
@@ -205,7 +206,7 @@ def item_spacings(source, n, spacing):
 
 def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False,
                      spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None, min_component=None,
-                     opening=None, closing=None, morph_per_slice=False, device_load=None, keep_masks=False):
+                     opening=None, closing=None, morph_per_slice=False, device_load=None, keep_masks=False, regions=False):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -244,7 +245,13 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     device_load (None: as the source was built; True / False): the source's volumes are built on the device from the payloads of their
     files (DeviceEvalSource.set_device_load); the tables and lines are the same either way.
     keep_masks=True: out["masks"] receives the list of every volume's final mask (uint8 [D,H,W] on the device, the end of the clean-up
-    chain where one is on); nothing else changes."""
+    chain where one is on); nothing else changes.
+    regions=True: the region statistics of VolumeSegmenter(regions=True) (rpnet_amd.regions): two more device tables, int64
+    [n_items, 2, K, 20] and fp64 [n_items, 2, K, 2] (the final mask at the end of the chain, then the labels, with the query image), are
+    fetched once with the others and arrive as out["regions_i"] and out["regions_f"].  A spacing (a triple or "header") is then accepted
+    without surface=True (out["spacing"] holds the spacings used).  Every item line gains, after the fields above,
+    ` vol <pred> (<truth>) rvd <x> cdist <x>` in voxels, under a spacing ` vol <pred> (<truth>) ml rvd <x> cdist <x> mm`; every class line
+    the means over the items where the figure is not None.  With regions=False nothing changes."""
     from .utils import nrrd
     from .volume import check_min_component
     if device_load is not None:
@@ -264,7 +271,7 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
         raise ValueError("evaluate_dataset: min_component in mm3 needs a spacing (a triple or 'header')")
     classes = config["eval_classes"]
     n = len(source) if n_items is None else min(n_items, len(source))
-    if ((spacing is not None and not mm3) or surface_tolerance is not None) and not surface:
+    if ((spacing is not None and not mm3 and not regions) or surface_tolerance is not None) and not surface:
         raise ValueError("evaluate_dataset: spacing and surface_tolerance act on the surface distances; give surface=True")
     if surface_tolerance is not None and spacing is None:
         raise ValueError("evaluate_dataset: surface_tolerance is a distance in millimetres; give spacing= as well")
@@ -273,7 +280,8 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     WI, WF = (SS.IROW, SS.FROW) if mm else (SF.IROW, SF.FROW)
     seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False, surface_tolerance=surface_tolerance,
                           fill_holes=fill_holes, hole_connectivity=hole_connectivity, max_hole=max_hole, min_component=min_component,
-                          **(dict(opening=opening, closing=closing, morph_per_slice=morph_per_slice) if morph_on else {}))
+                          **(dict(opening=opening, closing=closing, morph_per_slice=morph_per_slice) if morph_on else {}),
+                          **(dict(regions=True) if regions else {}))
     dev = next(net.parameters()).device
     T, K = net.num_iter, 2
     table = torch.zeros((n, T + 2, K - 1, 3), device=dev, dtype=torch.int64)
@@ -286,6 +294,8 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     post_f = torch.zeros((n, K - 1, WF), device=dev, dtype=torch.float64) if chain and surface else None
     post_w = torch.zeros((n, K - 1, 2 * PP.STATS_ROW), device=dev, dtype=torch.int64) if holes_on or small_on else None
     post_m = torch.zeros((n, K - 1, 2 * MO.STATS_ROW), device=dev, dtype=torch.int64) if morph_on else None
+    reg_i = torch.zeros((n, 2, K, RG.IROW), device=dev, dtype=torch.int64) if regions else None
+    reg_f = torch.zeros((n, 2, K, RG.FROW), device=dev, dtype=torch.float64) if regions else None
     meta, masks = [], []
     for j in range(n):
         s = source.item(j)
@@ -298,6 +308,8 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             extra["post_stats_out"] = post_w[j]
         if post_m is not None:
             extra["morph_stats_out"] = post_m[j]
+        if regions:
+            extra["regions_out"] = (reg_i[j], reg_f[j])
         res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j],
                   **extra)
         ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
@@ -338,6 +350,13 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             post_i, post_f = post_i.cpu().numpy(), post_f.cpu().numpy()
             if out is not None:
                 out["post_surface_mm_i" if mm else "post_surface_i"], out["post_surface_mm_f" if mm else "post_surface_f"] = post_i, post_f
+    reg_fig = defaultdict(list)
+    if regions:
+        reg_i, reg_f = reg_i.cpu().numpy(), reg_f.cpu().numpy()
+        if out is not None:
+            out["regions_i"], out["regions_f"] = reg_i, reg_f
+            if mm:
+                out["spacing"] = list(spacings)
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
     if save_pred:
         os.makedirs(save_pred, exist_ok=True)
@@ -377,6 +396,10 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             open_fig[name].append(op)
             close_fig[name].append(cl)
             line += MO.line_suffix(op, cl)
+        if regions:
+            fig = RG.region_figures(reg_i[j], reg_f[j], spacings[j])[0]
+            reg_fig[name].append(fig)
+            line += RG.region_line_suffix(fig, mm)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
@@ -388,5 +411,6 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
                   + (CC.mean_suffix(lcc_dice[name], lcc_fig[name], lcc_surf[name] if surface else None, unit="mm" if mm else "") if conn else "")
                   + (PP.mean_suffix(holes_fig[name] if holes_on else None, small_fig[name] if small_on else None) if post_w is not None else "")
                   + (MO.mean_suffix(open_fig[name] if open_r is not None else None, close_fig[name] if close_r is not None else None)
-                     if post_m is not None else ""))
+                     if post_m is not None else "")
+                  + (RG.region_mean_suffix(reg_fig[name], mm) if regions else ""))
     return dsc_affine, dsc_fewshot, dsc_ref

@@ -339,6 +339,23 @@ SIDE_ABIS_AFTER_DEEDS = [
     ("rpnet_fusion_abi.h", "label-fusion", "rpnet_fusion_abi_version", FUSION_ABI_VERSION, _FUSION_SIGS),
 ]
 
+# region statistics of a segmented volume (per label the count, box, coordinate moments and the intensity sums of an image):
+# include/rpnet_region_abi.h (ledger: tests/regions_abi_ledger.py).  The fifteenth side family.  tests/test_host_fusion_abi_ledger.py holds
+# SIDE_ABIS_AFTER_DEEDS to the one row above, so this family stands in a further table of the same form; load() binds and checks
+# ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD + SIDE_ABIS_AFTER_DEEDS +
+# SIDE_ABIS_AFTER_FUSION.
+_REGION_SIGS = {
+    "rpnet_region_abi_version": (ci, []),
+    "rpnet_region_workspace_bytes": (cs, [ci, ci, ci, ci]),
+    # labels, label_kind, image, image_kind, D, H, W, lo, L, rows_i, rows_f, row, n_rows, workspace, workspace_bytes, stream
+    "rpnet_region_stats": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+REGION_ABI_SYMBOLS = tuple(_REGION_SIGS)
+REGION_ABI_VERSION = 1     # RPNET_REGION_ABI_VERSION of include/rpnet_region_abi.h
+SIDE_ABIS_AFTER_FUSION = [
+    ("rpnet_region_abi.h", "region-statistics", "rpnet_region_abi_version", REGION_ABI_VERSION, _REGION_SIGS),
+]
+
 
 def lib_path():
     return _LIB_PATH
@@ -357,7 +374,7 @@ def load():
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
         side_abis = (ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD
-                     + SIDE_ABIS_AFTER_DEEDS)
+                     + SIDE_ABIS_AFTER_DEEDS + SIDE_ABIS_AFTER_FUSION)
         for sigs in [_SIGS] + [family[4] for family in side_abis]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)

@@ -19,6 +19,7 @@ from . import components as CC
 from . import hip
 from . import morphology as MO
 from . import postprocess as PP
+from . import regions as RG
 from . import surface as SF
 from . import surface_spacing as SS
 from .graph import GraphedEval
@@ -26,9 +27,11 @@ from .graph import GraphedEval
 
 class VolumeResult(namedtuple("VolumeResult", ["mask", "counts", "dice"])):
     """(mask, counts, dice) of a volume; `surface` beside them: None, or the surface distances of VolumeSegmenter(surface=True);
-    `post`: None, or what VolumeSegmenter(keep_largest=...) measured on the mask filtered to its largest components"""
+    `post`: None, or what VolumeSegmenter(keep_largest=...) measured on the mask filtered to its largest components; `regions`: None, or
+    the region statistics of VolumeSegmenter(regions=True)"""
     surface = None
     post = None
+    regions = None
 
 
 # One GraphedEval per net, shared by every VolumeSegmenter of that net.  A captured graph holds the addresses of the net's weight
@@ -218,10 +221,19 @@ class VolumeSegmenter:
                   is without them.
       morph_stats_out  int64 [K-1, 8] on the net's device (needs post_out): columns 0..3 take the statistics row of the opening, 4..7
                   that of the closing (the columns of a stage that is off are left as they are); 'opening' and 'closing' of `post`
-                  are None."""
+                  are None.
+      regions=True  once the volume is complete (after the clean-up chain where one is on), one `rpnet_region_stats` call
+                  (rpnet_amd.regions.region_stats) on the final mask and, with query_labels, one on the labels, both with the query
+                  image and without the background: count, box, coordinate moments and intensity sums of every label.  The result's
+                  `regions` is a dict: 'rows_i' int64 [2, K, 20] and 'rows_f' float64 [2, K, 2] on the host (prediction, then labels;
+                  the second row is empty without query_labels), 'pred' and 'truth' the per-label figures of regions.derive under the
+                  spacing, 'figures' per foreground class those of regions.compare (None without query_labels).  The two small tables
+                  cross to the host once per volume.  Nothing else changes.
+      regions_out (int64 [2, K, 20], float64 [2, K, 2]) on the net's device (needs regions=True): the rows are written there, nothing
+                  crosses to the host for them and the result's `regions` is None."""
 
     def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None, fill_holes=False,
-                 hole_connectivity=None, max_hole=None, min_component=None, opening=None, closing=None, morph_per_slice=False):
+                 hole_connectivity=None, max_hole=None, min_component=None, opening=None, closing=None, morph_per_slice=False, regions=False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.spacing = None if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
@@ -241,6 +253,7 @@ class VolumeSegmenter:
         self.opening = None if opening is None else MO.check_radius(opening, "VolumeSegmenter: opening")
         self.closing = None if closing is None else MO.check_radius(closing, "VolumeSegmenter: closing")
         self.morph_per_slice = bool(morph_per_slice)
+        self.regions = bool(regions)
         if self.morph_per_slice and self.opening is None and self.closing is None:
             raise ValueError("VolumeSegmenter: morph_per_slice needs opening or closing")
         self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
@@ -380,8 +393,25 @@ class VolumeSegmenter:
                 post["surface"] = self._figures(surf[0], surf[1], spacing)
         return post
 
+    def _regions(self, final, labels, image, K, regions_out, spacing=None):
+        """the region rows of the final mask (0) and of the labels (1), labels 1 .. K-1, with the query image"""
+        if regions_out is not None:
+            tables = tuple(regions_out)
+        else:
+            tables = (torch.zeros((2, K, RG.IROW), device=final.device, dtype=torch.int64),
+                      torch.zeros((2, K, RG.FROW), device=final.device, dtype=torch.float64))
+        RG.region_stats(final, image, n_labels=K, out=tables, row=0)
+        if labels is not None:
+            RG.region_stats(labels, image, n_labels=K, out=tables, row=1)
+        if regions_out is not None:
+            return None
+        rows_i, rows_f = tables[0].cpu().numpy(), tables[1].cpu().numpy()
+        return {"rows_i": rows_i, "rows_f": rows_f, "pred": RG.derive(rows_i[0], rows_f[0], spacing),
+                "truth": RG.derive(rows_i[1], rows_f[1], spacing) if labels is not None else None,
+                "figures": RG.region_figures(rows_i, rows_f, spacing) if labels is not None else None}
+
     def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None,
-                 post_out=None, spacing=None, post_stats_out=None, morph_stats_out=None):
+                 post_out=None, spacing=None, post_stats_out=None, morph_stats_out=None, regions_out=None):
         dev = next(self.net.parameters()).device
         morph = self.opening is not None or self.closing is not None
         chain = bool(self.keep_largest) or self.fill_holes is not None or self.min_component is not None or morph
@@ -435,6 +465,12 @@ class VolumeSegmenter:
                 raise ValueError(f"morph_stats_out must be a contiguous int64 [{K - 1}, {2 * MO.STATS_ROW}] tensor")
             if morph_stats_out.device != dev:
                 raise ValueError(f"morph_stats_out is on {morph_stats_out.device}, the net on {dev}")
+        if regions_out is not None:
+            if not self.regions:
+                raise ValueError("regions_out needs VolumeSegmenter(regions=True)")
+            RG.check_regions_out(regions_out, K)
+            if any(t.device != dev for t in regions_out):
+                raise ValueError(f"regions_out is on {regions_out[0].device}, the net on {dev}")
         nb = -(-S // B)
         pad = nb * B - S
 
@@ -475,6 +511,8 @@ class VolumeSegmenter:
                           mask[sl], mask_src=T, K=K, _table=tab)
             surface = self._surface(mask[:S], appr[:S], labels[:S], K, surface_out, spacing) if self.surface and labels is not None else None
             post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out, spacing, post_stats_out, morph_stats_out) if chain else None
+            regions = self._regions(post["mask"] if chain else mask[:S], labels[:S] if labels is not None else None, qi[:S, 0], K, regions_out,
+                                    spacing) if self.regions else None
         if counts is None or counts_out is not None:
             res = VolumeResult(mask[:S], None, None)
         else:
@@ -487,4 +525,6 @@ class VolumeSegmenter:
             res.surface = surface
         if post is not None:
             res.post = post
+        if regions is not None:
+            res.regions = regions
         return res

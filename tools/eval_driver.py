@@ -26,6 +26,9 @@ each figure followed by `mm`, and with a tolerance the normalised surface Dice `
 support volume per query, then the reference's "Average performance" block (test_rpnet.py:112-145; rpnet_amd.fusion.evaluate_runs).
 --fuse fuses every query's R final masks on the device by majority vote or STAPLE and prints the fused Dice beside the runs' own;
 --fuse-all-voxels lets the voxels on which all runs agree take part in STAPLE's EM; --save-pred then writes the fused mask.
+--regions (needs --device-items): every item line gains ` vol <pred> (<truth>) rvd <x> cdist <x>`, the volume of the final mask (of the
+labels), their relative volume difference and the distance of their centroids, in voxels, under --spacing in ml and mm
+(rpnet_amd.regions), every class line their means.
 """
 import argparse
 import os
@@ -284,6 +287,9 @@ def build_parser():
                          "average over the runs (rpnet_amd.fusion.evaluate_runs)")
     ap.add_argument("--fuse", choices=("vote", "staple"), default=None,
                     help="with --runs: fuse every query's masks of the R runs on the device (rpnet_amd.fusion); --save-pred writes the fused mask")
+    ap.add_argument("--regions", action="store_true",
+                    help="with --device-items: volume, relative volume difference and centroid distance of every final mask against the "
+                         "labels (rpnet_amd.regions), in voxels, or in ml and mm under --spacing")
     ap.add_argument("--fuse-all-voxels", action="store_true", help="with --fuse staple: the voxels all runs agree on take part in the EM")
     return ap
 
@@ -302,6 +308,8 @@ def main():
         raise SystemExit("--device-load needs --device-items")
     if a.runs is not None and not a.device_items:
         raise SystemExit("--runs needs --device-items")
+    if a.regions and not a.device_items:
+        raise SystemExit("--regions needs --device-items")
     if (a.fuse or a.fuse_all_voxels) and a.runs is None:
         raise SystemExit("--fuse and --fuse-all-voxels need --runs")
     min_component = parse_min_component(a.min_component)
@@ -317,6 +325,8 @@ def main():
     post = dict(fill_holes=a.fill_holes or False, max_hole=a.max_hole, min_component=min_component)
     if opening is not None or closing is not None:
         post.update(opening=opening, closing=closing, morph_per_slice=a.morph_slice)
+    if a.regions:
+        post.update(regions=True)
     loader = None if a.device_items else FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
     net = model_factory[args.net](pretrained_path=config.get("pretrained_path"),
                                   cfg={"align": True, "backbone": config.get("backbone", "vgg")}, backbone_cfg=config).cuda()
