@@ -280,6 +280,80 @@ def conv_wgrad(x0, x1, dy, taps=9, dilation=1, upsample=0, in_scale=None, in_sca
                                      for kw in range(3)], -1) for kh in range(3)], -2)
 
 
+# ------------------------------ convolution forward and input gradient (nn.Conv2d and its autograd wrt the input, include/rpnet_abi.h), NHWC
+def _row_factor(s, mode, shape, dtype):
+    s = _c(s, dtype).reshape(shape)[..., None]
+    return s if mode == 1 else 1 - s
+
+
+def conv_fwd(x0, x1, w, bias=None, taps=9, dilation=1, upsample=0, in_scale=None, in_scale_mode=0, ep_scale=None, ep_shift=None,
+             ep_relu=0, groups=1, out_scale=None, out_scale_mode=0, prev=None, dtype=F64):
+    """one launch of rpnet_conv_fwd -> (the final output, acc + bias) [N, H, W, cout].  The sources x0 | x1 [N, h, w, C0 | C1] are
+    concatenated along C (x1 None: one source), multiplied per SOURCE pixel by in_scale [N, h, w] (mode 1) or 1 - in_scale (mode 2),
+    nearest x2 up-sampled (upsample = 1) and convolved with w [cout, cin, k, k] (taps 9: k = 3, tap spacing and zero padding
+    max(dilation, 1); taps 1: k = 1) through F.conv2d; + bias.  That sum is what stats_partial adds up.  Then, in the kernels'
+    order: * ep_scale[g] + ep_shift[g] ([groups, cout]; image n is in group n // (N / groups)), ReLU, * out_scale [N, H, W]
+    (mode 1) or 1 - out_scale (mode 2) per OUTPUT pixel, + prev (accumulate)."""
+    x = _c(x0, dtype) if x1 is None else torch.cat([_c(x0, dtype), _c(x1, dtype)], -1)
+    if in_scale_mode:
+        x = x * _row_factor(in_scale, in_scale_mode, x.shape[:3], dtype)
+    if upsample:
+        x = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    d = max(int(dilation), 1) if taps == 9 else 0
+    pre = _nhwc(F.conv2d(x.permute(0, 3, 1, 2), _c(w, dtype), _c(bias, dtype), padding=d, dilation=max(d, 1)))
+    y = pre
+    if ep_scale is not None:
+        y = y * _per_image(_c(ep_scale, dtype).reshape(groups, -1), y.shape[0]) + _per_image(_c(ep_shift, dtype).reshape(groups, -1), y.shape[0])
+    if ep_relu:
+        y = torch.relu(y)
+    if out_scale_mode:
+        y = y * _row_factor(out_scale, out_scale_mode, y.shape[:3], dtype)
+    if prev is not None:
+        y = y + _c(prev, dtype)
+    return y, pre
+
+
+def conv_dgrad(dy, w, taps=9, dilation=1, co_split=None, out_scale=None, out_scale_mode=0, prev=None, upsample=0, dtype=F64):
+    """the input gradient of y = conv(x, w), w [cout, cin, k, k], from dy [N, H, W, cout]: the same convolution with the transposed,
+    flipped weight -> dx [N, H, W, cin], * out_scale [N, H, W] (mode 1) or 1 - out_scale (mode 2), + prev (accumulate), through
+    upsample2_bwd for a layer that reads its input through the nearest x2 up-sampling, then cut along C at co_split = (Co0, Co1)
+    into the gradients of the two concatenated sources -> a list of one or two tensors"""
+    wt = _c(w, dtype).transpose(0, 1).flip(2, 3)
+    dx, _ = conv_fwd(dy, None, wt, None, taps, dilation, 0, out_scale=out_scale, out_scale_mode=out_scale_mode, prev=prev, dtype=dtype)
+    if upsample:
+        dx = upsample2_bwd(dx, dtype)
+    if co_split is None or not co_split[1]:
+        return [dx]
+    return [dx[..., :co_split[0]].contiguous(), dx[..., co_split[0]:].contiguous()]
+
+
+def _upconv_collapsed(x, wc, bias):
+    # phase (py, px) of the output is a 2 x 2 convolution of the zero-padded SOURCE whose window starts at (Y + py - 1, X + px - 1)
+    N, h, w, _ = x.shape
+    cout = wc.shape[0] // 4
+    xp = F.pad(x.permute(0, 3, 1, 2), (1, 1, 1, 1))
+    y = torch.zeros(N, cout, 2 * h, 2 * w, dtype=x.dtype)
+    for py in range(2):
+        for px in range(2):
+            o = F.conv2d(xp, wc[(py * 2 + px) * cout:(py * 2 + px + 1) * cout], bias)          # [N, cout, h + 1, w + 1]
+            y[:, :, py::2, px::2] = o[:, :, py:py + h, px:px + w]
+    return _nhwc(y)
+
+
+def upconv_collapsed(x, wc, bias=None, dtype=F64):
+    """nn.Upsample(2) -> Conv2d 3 x 3 from its COLLAPSED weights wc [4 cout, cin, 2, 2] (phase-major, rpnet_upconv_collapse_weights):
+    x [N, h, w, cin] -> y [N, 2 h, 2 w, cout], y[2 Y + py, 2 X + px] = sum_{r, c} wc[(py, px)][r][c] x[Y + py + r - 1, X + px + c - 1]"""
+    return _upconv_collapsed(_c(x, dtype), _c(wc, dtype), _c(bias, dtype))
+
+
+def upconv_collapsed_dgrad(dy, wc, dtype=F64):
+    """its input gradient through autograd: dy [N, 2 h, 2 w, cout] -> dx [N, h, w, cin]"""
+    dy, wc = _c(dy, dtype), _c(wc, dtype)
+    x = torch.zeros(dy.shape[0], dy.shape[1] // 2, dy.shape[2] // 2, wc.shape[1], dtype=dtype, requires_grad=True)
+    (g,) = torch.autograd.grad(_upconv_collapsed(x, wc, None), x, dy)
+    return g
+
+
 # ------------------------- the first layer, Cin = 1 (Conv1.conv.0 of net/unet.py:407 with img_ch = 1, conv_block of net/modules.py:47-49)
 def _per_image(v, N):
     """[groups, C] -> [N, 1, 1, C]: image n is in statistic group n // (N // groups)"""
