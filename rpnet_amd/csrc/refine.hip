@@ -150,11 +150,18 @@ __global__ __launch_bounds__(256) void refine_glue_fwd_kernel(const RefineFwd a)
             const f32x4 u0 = *reinterpret_cast<const f32x4*>(a.x + off), u1 = *reinterpret_cast<const f32x4*>(a.x + off + 4);
             const float f1 = msk[pi], f2 = 1.f - f1;
             float vk[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]}, vq[8];
+            // x * f is rounded to fp32 ONCE and stays a value of its own (the empty asm is opaque to the compiler and emits nothing, as in
+            // split_f16_kernel; __fmul_rn is a plain product here and does not keep it apart): otherwise the residual of the first plane is
+            // selected as fma(x, f, -h) and the three bf16 planes add up to the unrounded product instead of the fp32(x * f) that
+            // split_bf16_kernel splits and the header states.
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { vq[q] = __fmul_rn(vk[q], f2); vk[q] = __fmul_rn(vk[q], f1); }     // (x * f rounded once: no contraction with 1 - m)
+            for (int q = 0; q < 8; ++q) {
+                vq[q] = vk[q] * f2; vk[q] = vk[q] * f1;
+                asm("" : "+v"(vk[q])); asm("" : "+v"(vq[q]));
+            }
             if (NP <= 2) {
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { vk[q] *= inv; vq[q] *= inv; }
+                for (int q = 0; q < 8; ++q) { vk[q] *= inv; vq[q] *= inv; asm("" : "+v"(vk[q])); asm("" : "+v"(vq[q])); }
             }
             u32x4 ok[NP], oq[NP];
             split8<NP>(vk, ok);

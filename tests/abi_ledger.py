@@ -13,6 +13,7 @@ WGRAD64 = "tests/test_gpu_wgrad_fp64.py"
 CONV164 = "tests/test_gpu_conv1_fp64.py"
 CONV64 = "tests/test_gpu_conv_fp64.py"         # forward and input gradient at every dispatch edge: tests/conv_cases.py
 OPERANDS = "tests/test_gpu_operands.py"        # the splitters and packers bit for bit: tests/operand_cases.py
+GLUE64 = "tests/test_gpu_glue_fp64.py"         # the fused refinement glue, the multi-tensor loss and the objective: tests/glue_cases.py
 
 COVERED_BY = {
     "rpnet_last_error_string": [VOLUME + "::test_tally_error_returns", SMALL + "::test_refusals"],
@@ -92,20 +93,20 @@ COVERED_BY = {
     "rpnet_bilinear_up_fwd": [SMALL + "::test_bilinear", SMALL + "::test_bilinear_forward_takes_a_ratio_that_is_no_integer"],
     "rpnet_bilinear_up_bwd": [SMALL + "::test_bilinear", SMALL + "::test_refusals"],
     "rpnet_softmax_thresh_pool": [SMALL + "::test_softmax_thresh_pool", SMALL + "::test_softmax_tie_block_counts_nothing"],
-    "rpnet_refine_glue_supported": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit"],
-    "rpnet_refine_glue_fwd": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit"],
-    "rpnet_refine_glue_bwd_workspace_bytes": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit"],
-    "rpnet_refine_glue_bwd": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit"],
+    "rpnet_refine_glue_supported": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit", GLUE64 + "::test_glue_supported_answers", GLUE64 + "::test_glue_forward"],
+    "rpnet_refine_glue_fwd": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit", GLUE64 + "::test_glue_forward", GLUE64 + "::test_glue_forward_with_operand_planes", GLUE64 + "::test_glue_hard_mask_of_a_tie_is_zero", GLUE64 + "::test_glue_zero_patch", GLUE64 + "::test_refusals"],
+    "rpnet_refine_glue_bwd_workspace_bytes": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit", GLUE64 + "::test_glue_backward", GLUE64 + "::test_glue_supported_answers"],
+    "rpnet_refine_glue_bwd": [OPS + "::test_refine_glue_is_the_separate_launches_bit_for_bit", GLUE64 + "::test_glue_backward", GLUE64 + "::test_glue_zero_patch", GLUE64 + "::test_refusals"],
     "rpnet_rowdot_scale": [SMALL + "::test_rowdot_scale", SMALL + "::test_refusals"],
     "rpnet_softmax_pool_bwd": [SMALL + "::test_softmax_thresh_pool", SMALL + "::test_refusals"],
     # ---- losses, evaluation tallies, align pieces
     "rpnet_loss_workspace_bytes": [SMALL + "::test_dice_ce"],
     "rpnet_dice_ce_fwd": [SMALL + "::test_dice_ce", SMALL + "::test_refusals"],
     "rpnet_dice_ce_bwd": [SMALL + "::test_dice_ce", SMALL + "::test_refusals"],
-    "rpnet_dice_ce_multi_fwd": [OPS + "::test_dice_ce_sum_matches_separate_calls"],
-    "rpnet_dice_ce_multi_bwd": [OPS + "::test_dice_ce_sum_matches_separate_calls"],
-    "rpnet_objective_fwd": [OPS + "::test_objective_is_the_tensor_expression_bit_for_bit"],
-    "rpnet_objective_bwd": [OPS + "::test_objective_is_the_tensor_expression_bit_for_bit"],
+    "rpnet_dice_ce_multi_fwd": [OPS + "::test_dice_ce_sum_matches_separate_calls", GLUE64 + "::test_multi_loss_and_objective", GLUE64 + "::test_refusals"],
+    "rpnet_dice_ce_multi_bwd": [OPS + "::test_dice_ce_sum_matches_separate_calls", GLUE64 + "::test_multi_loss_and_objective", GLUE64 + "::test_refusals"],
+    "rpnet_objective_fwd": [OPS + "::test_objective_is_the_tensor_expression_bit_for_bit", GLUE64 + "::test_multi_loss_and_objective", GLUE64 + "::test_refusals"],
+    "rpnet_objective_bwd": [OPS + "::test_objective_is_the_tensor_expression_bit_for_bit", GLUE64 + "::test_multi_loss_and_objective", GLUE64 + "::test_refusals"],
     "rpnet_seg_tally": [VOLUME + "::test_tally_error_returns", VOLUME + "::test_captured_launch_follows_n_valid"],
     "rpnet_argmax_masks": [SMALL + "::test_argmax_masks", SMALL + "::test_refusals"],
     "rpnet_align_labels": [SMALL + "::test_align_labels", SMALL + "::test_refusals"],

@@ -489,3 +489,51 @@ def bn_eval_bwd(dz, y, stats, groups=1, dtype=F64):
     z = torch.relu((y - _per_image(mu, N)) * _per_image(inv, N) * _per_image(gamma, N) + _per_image(beta, N))
     dy, dg, db = torch.autograd.grad(z, (y, gamma, beta), _c(dz, dtype))
     return dy, dg.sum(0), db.sum(0)
+
+
+# ---------------- the glue between two refinement iterations (net/rp_net.py:65-69,301-311; csrc/refine.hip): compositions of the above
+def refine_glue(y, scale, shift, proto, scaler=20.0, soft=False, dtype=F64):
+    """y [B, h, w, F], scale / shift [F] or None (no BatchNorm: z = y), proto [B, K, F] ->
+    (z [B, h, w, F], pred [B, K, h, w], logits [B, K, 4h, 4w], mask [B, h, w])"""
+    B, h, w, Fc = y.shape
+    K = proto.shape[1]
+    z = _c(y, dtype) if scale is None else bn_relu(y, scale, shift, dtype=dtype)
+    pred = cosine_match(z.reshape(B, h * w, Fc), proto, scaler, dtype).reshape(B, K, h, w)
+    logits = bilinear_up(pred.reshape(B * K, h, w), 4 * h, 4 * w, dtype).reshape(B, K, 4 * h, 4 * w)
+    return z, pred, logits, softmax_thresh_pool(logits, 4, soft, dtype)
+
+
+def refine_glue_bwd(dlogits, f, proto, scaler=20.0, dtype=F64):
+    """dlogits [B, K, 4h, 4w], f [B, h, w, F] (the features after BatchNorm + ReLU) -> (df [B, h, w, F], dproto [B, K, F])"""
+    B, K, H, W = dlogits.shape
+    h, w = H // 4, W // 4
+    dpred = bilinear_up_bwd(torch.as_tensor(dlogits).reshape(B * K, H, W), h, w, dtype).reshape(B, K, h * w)
+    df, dproto = cosine_match_bwd(torch.as_tensor(f).reshape(B, h * w, -1), proto, dpred, scaler, dtype)
+    return df.reshape(B, h, w, -1), dproto
+
+
+def hard_mask_margin(logits, dtype=F64):
+    """|l1 - logsumexp(the other classes)| [B, H, W]: the distance of softmax[:, 1] > 0.5 from its boundary"""
+    lg = _c(logits, dtype)
+    return (lg[:, 1] - torch.logsumexp(torch.cat([lg[:, :1], lg[:, 2:]], 1), 1)).abs()
+
+
+# ---------------------------------------------- the multi-tensor loss and the training objective (csrc/loss.hip), per logit tensor
+def dice_ce_stats(logits, labels, dtype=F64):
+    """-> [B + 1, 2K + 2]: per sample, then summed over the batch: inter_k = sum p_k [label = k], card_k = sum p_k + [label = k],
+    ce_sum = - sum log_softmax[label], count = the pixels (nothing ignored)"""
+    lg, lab = _c(logits, dtype), torch.as_tensor(labels).cpu()
+    K = lg.shape[1]
+    one_hot = torch.eye(K, dtype=dtype)[lab].permute(0, 3, 1, 2)
+    p = torch.softmax(lg, dim=1)
+    ce = F.cross_entropy(lg, lab, reduction="none").sum(dim=(1, 2))
+    rows = torch.cat([(p * one_hot).sum(dim=(2, 3)), (p + one_hot).sum(dim=(2, 3)), ce[:, None],
+                      torch.full((lg.shape[0], 1), float(lg.shape[2] * lg.shape[3]), dtype=dtype)], 1)
+    return torch.cat([rows, rows.sum(0, keepdim=True)], 0)
+
+
+def objective(logits, weights, labels, extra=None, extra_scale=0.0, dtype=F64):
+    """-> (loss_z [n] = dice_ce of every tensor, total = sum_z w_z loss_z + extra_scale * extra)"""
+    losses = torch.stack([dice_ce(t, labels, dtype=dtype) for t in logits])
+    total = (torch.as_tensor(weights, dtype=dtype) * losses).sum()
+    return losses, total if extra is None else total + extra_scale * _c(extra, dtype).reshape(())
