@@ -14,6 +14,7 @@ CONV164 = "tests/test_gpu_conv1_fp64.py"
 CONV64 = "tests/test_gpu_conv_fp64.py"         # forward and input gradient at every dispatch edge: tests/conv_cases.py
 OPERANDS = "tests/test_gpu_operands.py"        # the splitters and packers bit for bit: tests/operand_cases.py
 GLUE64 = "tests/test_gpu_glue_fp64.py"         # the fused refinement glue, the multi-tensor loss and the objective: tests/glue_cases.py
+AUG64 = "tests/test_gpu_augment_fp64.py"       # the train-time augmentation against the header's rules: tests/augment_ref_cases.py
 
 COVERED_BY = {
     "rpnet_last_error_string": [VOLUME + "::test_tally_error_returns", SMALL + "::test_refusals"],
@@ -124,10 +125,15 @@ COVERED_BY = {
     "rpnet_displacement_warp": [REG + "::test_hip_demons_stage_vs_oracle", REG64 + "::test_warps",
         REG64 + "::test_registration_refusals"],
     # ---- train-time augmentation
-    "rpnet_slice_minmax": [AUGMENT + "::test_gamma_affine_matches_host"],
-    "rpnet_augment_affine": [AUGMENT + "::test_gamma_affine_matches_host"],
-    "rpnet_elastic_field": [AUGMENT + "::test_elastic_field_matches_scipy"],
-    "rpnet_elastic_apply": [AUGMENT + "::test_elastic_slices_match_host"],
+    "rpnet_slice_minmax": [AUGMENT + "::test_gamma_affine_matches_host", AUG64 + "::test_slice_minmax", AUG64 + "::test_sixty_five_thousand_slices",
+                           AUG64 + "::test_production_size_once", AUG64 + "::test_no_slices_is_success_and_writes_nothing", AUG64 + "::test_refusals"],
+    "rpnet_augment_affine": [AUGMENT + "::test_gamma_affine_matches_host", AUG64 + "::test_affine_exact_maps", AUG64 + "::test_affine_drawn_maps",
+                             AUG64 + "::test_affine_image_path", AUG64 + "::test_sixty_five_thousand_slices", AUG64 + "::test_production_size_once",
+                             AUG64 + "::test_no_slices_is_success_and_writes_nothing", AUG64 + "::test_refusals"],
+    "rpnet_elastic_field": [AUGMENT + "::test_elastic_field_matches_scipy", AUG64 + "::test_elastic_field", AUG64 + "::test_production_size_once",
+                            AUG64 + "::test_refusals"],
+    "rpnet_elastic_apply": [AUGMENT + "::test_elastic_slices_match_host", AUG64 + "::test_elastic_apply_crafted", AUG64 + "::test_elastic_apply_drawn",
+                            AUG64 + "::test_production_size_once", AUG64 + "::test_no_slices_is_success_and_writes_nothing", AUG64 + "::test_refusals"],
 }
 
 # names on the Python side through which a test reaches a symbol it does not spell out
