@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import augment as A
+from . import component_stats as CS
 from . import components as CC
 from . import morphology as MO
 from . import postprocess as PP
@@ -206,7 +207,8 @@ def item_spacings(source, n, spacing):
 
 def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, save_pred=None, out=None, surface=False, keep_largest=False,
                      spacing=None, surface_tolerance=None, fill_holes=False, hole_connectivity=None, max_hole=None, min_component=None,
-                     opening=None, closing=None, morph_per_slice=False, device_load=None, keep_masks=False, regions=False):
+                     opening=None, closing=None, morph_per_slice=False, device_load=None, keep_masks=False, regions=False,
+                     components=False):
     """tools/eval_driver.py:evaluate over a DeviceEvalSource: the same printed lines (with both image similarity figures of
     test_rpnet.py:229-230: query against the fully warped and against the affine-warped support) and the same three dictionaries.
     The Dice tallies of all items are summed on the device into one int64 table [n_items, T+2, K-1, 3] and the NCC figures written into
@@ -251,7 +253,14 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     fetched once with the others and arrive as out["regions_i"] and out["regions_f"].  A spacing (a triple or "header") is then accepted
     without surface=True (out["spacing"] holds the spacings used).  Every item line gains, after the fields above,
     ` vol <pred> (<truth>) rvd <x> cdist <x>` in voxels, under a spacing ` vol <pred> (<truth>) ml rvd <x> cdist <x> mm`; every class line
-    the means over the items where the figure is not None.  With regions=False nothing changes."""
+    the means over the items where the figure is not None.  With regions=False nothing changes.
+    components=True | max_components: the per-component tables of VolumeSegmenter(components=...) (rpnet_amd.component_stats): two
+    more device tables, int64 [n_items, 2, K-1, max_components, 24] and [n_items, 2, K-1, 4] (the final mask against the labels, then
+    the labels against the final mask), are fetched once with the others and arrive as out["components_rows"] and
+    out["components_head"].  A spacing is then accepted without surface=True.  Every item line gains, after the fields above,
+    ` comp <Cp> (<Ct>) det <detected>/<Ct> fp <n> fpvol <voxels>`, under a spacing `fpvol <x> mL`: the components of the prediction
+    (of the labels), the truth components the prediction overlaps, the predicted components that overlap no truth voxel and their
+    volume; every class line the means.  With components=False nothing changes."""
     from .utils import nrrd
     from .volume import check_min_component
     if device_load is not None:
@@ -271,7 +280,7 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
         raise ValueError("evaluate_dataset: min_component in mm3 needs a spacing (a triple or 'header')")
     classes = config["eval_classes"]
     n = len(source) if n_items is None else min(n_items, len(source))
-    if ((spacing is not None and not mm3 and not regions) or surface_tolerance is not None) and not surface:
+    if ((spacing is not None and not mm3 and not regions and not components) or surface_tolerance is not None) and not surface:
         raise ValueError("evaluate_dataset: spacing and surface_tolerance act on the surface distances; give surface=True")
     if surface_tolerance is not None and spacing is None:
         raise ValueError("evaluate_dataset: surface_tolerance is a distance in millimetres; give spacing= as well")
@@ -281,7 +290,7 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     seg = VolumeSegmenter(net, batch=batch, graphed=graphed, surface=surface, keep_largest=conn or False, surface_tolerance=surface_tolerance,
                           fill_holes=fill_holes, hole_connectivity=hole_connectivity, max_hole=max_hole, min_component=min_component,
                           **(dict(opening=opening, closing=closing, morph_per_slice=morph_per_slice) if morph_on else {}),
-                          **(dict(regions=True) if regions else {}))
+                          **(dict(regions=True) if regions else {}), **(dict(components=components) if components else {}))
     dev = next(net.parameters()).device
     T, K = net.num_iter, 2
     table = torch.zeros((n, T + 2, K - 1, 3), device=dev, dtype=torch.int64)
@@ -296,6 +305,9 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
     post_m = torch.zeros((n, K - 1, 2 * MO.STATS_ROW), device=dev, dtype=torch.int64) if morph_on else None
     reg_i = torch.zeros((n, 2, K, RG.IROW), device=dev, dtype=torch.int64) if regions else None
     reg_f = torch.zeros((n, 2, K, RG.FROW), device=dev, dtype=torch.float64) if regions else None
+    comp_n = CS.components_option(components)
+    comp_rows = torch.zeros((n, 2, K - 1, comp_n, CS.COMP_ROW), device=dev, dtype=torch.int64) if comp_n else None
+    comp_head = torch.zeros((n, 2, K - 1, CS.HEAD_WORDS), device=dev, dtype=torch.int64) if comp_n else None
     meta, masks = [], []
     for j in range(n):
         s = source.item(j)
@@ -310,6 +322,8 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             extra["morph_stats_out"] = post_m[j]
         if regions:
             extra["regions_out"] = (reg_i[j], reg_f[j])
+        if comp_n:
+            extra["components_out"] = (comp_rows[j], comp_head[j])
         res = seg(s["support_images"], s["support_labels"], s["query_images"], s["appr_query_labels"], s["query_labels"], counts_out=table[j],
                   **extra)
         ncc_pairs(s["query_images"], s["warped_supp"], s["support_images"][0][0], ncc, j)
@@ -357,6 +371,13 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             out["regions_i"], out["regions_f"] = reg_i, reg_f
             if mm:
                 out["spacing"] = list(spacings)
+    comp_fig = defaultdict(list)
+    if comp_n:
+        comp_rows, comp_head = comp_rows.cpu().numpy(), comp_head.cpu().numpy()
+        if out is not None:
+            out["components_rows"], out["components_head"] = comp_rows, comp_head
+            if mm:
+                out["spacing"] = list(spacings)
     dsc_affine, dsc_fewshot, dsc_ref = defaultdict(list), defaultdict(list), defaultdict(lambda: defaultdict(list))
     if save_pred:
         os.makedirs(save_pred, exist_ok=True)
@@ -400,6 +421,10 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
             fig = RG.region_figures(reg_i[j], reg_f[j], spacings[j])[0]
             reg_fig[name].append(fig)
             line += RG.region_line_suffix(fig, mm)
+        if comp_n:
+            fig = CS.detection_figures(comp_rows[j], comp_head[j], spacings[j])[0]
+            comp_fig[name].append(fig)
+            line += CS.detection_line_suffix(fig, mm)
         print(line)
         if save_pred:
             nrrd.write(os.path.join(save_pred, f"{pid}_{name}.nrrd"), masks[j].cpu().numpy(), encoding="gzip")
@@ -412,5 +437,6 @@ def evaluate_dataset(net, source, config, n_items=None, batch=8, graphed=True, s
                   + (PP.mean_suffix(holes_fig[name] if holes_on else None, small_fig[name] if small_on else None) if post_w is not None else "")
                   + (MO.mean_suffix(open_fig[name] if open_r is not None else None, close_fig[name] if close_r is not None else None)
                      if post_m is not None else "")
-                  + (RG.region_mean_suffix(reg_fig[name], mm) if regions else ""))
+                  + (RG.region_mean_suffix(reg_fig[name], mm) if regions else "")
+                  + (CS.detection_mean_suffix(comp_fig[name], mm) if comp_n else ""))
     return dsc_affine, dsc_fewshot, dsc_ref

@@ -356,6 +356,26 @@ SIDE_ABIS_AFTER_FUSION = [
     ("rpnet_region_abi.h", "region-statistics", "rpnet_region_abi_version", REGION_ABI_VERSION, _REGION_SIGS),
 ]
 
+# per-component statistics of a segmented volume (the dense renumbering of the sparse labels of rpnet_cc_label, then per component the
+# count, box, coordinate moments, exact sums of the quantised image and the overlap with a class of a second volume):
+# include/rpnet_compstat_abi.h (ledger: tests/compstat_abi_ledger.py).  The sixteenth side family.  tests/test_host_regions_abi_ledger.py
+# holds SIDE_ABIS_AFTER_FUSION to the one row above, so this family stands in a further table of the same form; load() binds and checks
+# it behind the others.
+_COMPSTAT_SIGS = {
+    "rpnet_compstat_abi_version": (ci, []),
+    "rpnet_compstat_workspace_bytes": (cs, [ci, ci, ci, ci]),
+    # labels, D, H, W, dense, stats, stats_row, n_rows, workspace, workspace_bytes, stream
+    "rpnet_compstat_rank": (ci, [vp, ci, ci, ci, vp, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+    # dense, image, image_kind, scale_log2, other, other_kind, other_cls, D, H, W, max_components, rows, row, n_rows, workspace,
+    # workspace_bytes, stream
+    "rpnet_compstat_table": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, vp, C.c_int64, C.c_int64, vp, cs, vp]),
+}
+COMPSTAT_ABI_SYMBOLS = tuple(_COMPSTAT_SIGS)
+COMPSTAT_ABI_VERSION = 1     # RPNET_COMPSTAT_ABI_VERSION of include/rpnet_compstat_abi.h
+SIDE_ABIS_AFTER_REGIONS = [
+    ("rpnet_compstat_abi.h", "component-statistics", "rpnet_compstat_abi_version", COMPSTAT_ABI_VERSION, _COMPSTAT_SIGS),
+]
+
 
 def lib_path():
     return _LIB_PATH
@@ -374,7 +394,7 @@ def load():
             raise RuntimeError(f"{_LIB_PATH} has ABI version {lib.rpnet_version()}, this binding was written for {ABI_VERSION} "
                                "(include/rpnet_abi.h RPNET_ABI_VERSION): rebuild it with `make -C rpnet_amd/csrc`")
         side_abis = (ALL_SIDE_ABIS + SIDE_ABIS_AFTER_PREP + SIDE_ABIS_AFTER_RESAMPLE + SIDE_ABIS_AFTER_SMOOTH + SIDE_ABIS_AFTER_VOLLOAD
-                     + SIDE_ABIS_AFTER_DEEDS + SIDE_ABIS_AFTER_FUSION)
+                     + SIDE_ABIS_AFTER_DEEDS + SIDE_ABIS_AFTER_FUSION + SIDE_ABIS_AFTER_REGIONS)
         for sigs in [_SIGS] + [family[4] for family in side_abis]:
             for name, (res, args) in sigs.items():
                 fn = getattr(lib, name, None)

@@ -15,6 +15,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from . import component_stats as CS
 from . import components as CC
 from . import hip
 from . import morphology as MO
@@ -28,10 +29,12 @@ from .graph import GraphedEval
 class VolumeResult(namedtuple("VolumeResult", ["mask", "counts", "dice"])):
     """(mask, counts, dice) of a volume; `surface` beside them: None, or the surface distances of VolumeSegmenter(surface=True);
     `post`: None, or what VolumeSegmenter(keep_largest=...) measured on the mask filtered to its largest components; `regions`: None, or
-    the region statistics of VolumeSegmenter(regions=True)"""
+    the region statistics of VolumeSegmenter(regions=True); `components`: None, or the per-component tables of
+    VolumeSegmenter(components=...)"""
     surface = None
     post = None
     regions = None
+    components = None
 
 
 # One GraphedEval per net, shared by every VolumeSegmenter of that net.  A captured graph holds the addresses of the net's weight
@@ -230,10 +233,21 @@ class VolumeSegmenter:
                   spacing, 'figures' per foreground class those of regions.compare (None without query_labels).  The two small tables
                   cross to the host once per volume.  Nothing else changes.
       regions_out (int64 [2, K, 20], float64 [2, K, 2]) on the net's device (needs regions=True): the rows are written there, nothing
-                  crosses to the host for them and the result's `regions` is None."""
+                  crosses to the host for them and the result's `regions` is None.
+      components=True | max_components  once the volume is complete (after the clean-up chain where one is on), per foreground class
+                  one rpnet_amd.component_stats.component_table chain (label, renumber, tally; connectivity 6) on the final mask
+                  with the labels as its `other` volume and, with query_labels, one on the labels with the final mask as theirs, both
+                  with the query image at the default scale.  True stands for 4096 components per class.  The result's `components`
+                  is a dict: 'rows' int64 [2, K-1, max_components, 24] and 'head' int64 [2, K-1, 4] on the host (prediction, then
+                  labels; the second is zero without query_labels), 'scale_log2', and 'figures', per foreground class the dict of
+                  component_stats.detection_figures (None without query_labels).  The tables cross to the host once per volume.
+                  Nothing else changes.
+      components_out (int64 [2, K-1, max_components, 24], int64 [2, K-1, 4]) on the net's device (needs components=...): the rows and
+                  head words are written there, nothing crosses to the host for them and the result's `components` is None."""
 
     def __init__(self, net, batch=8, graphed=True, surface=False, keep_largest=False, spacing=None, surface_tolerance=None, fill_holes=False,
-                 hole_connectivity=None, max_hole=None, min_component=None, opening=None, closing=None, morph_per_slice=False, regions=False):
+                 hole_connectivity=None, max_hole=None, min_component=None, opening=None, closing=None, morph_per_slice=False, regions=False,
+                 components=False):
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.spacing = None if spacing is None else SS.check_spacing(spacing, "VolumeSegmenter")
@@ -254,6 +268,7 @@ class VolumeSegmenter:
         self.closing = None if closing is None else MO.check_radius(closing, "VolumeSegmenter: closing")
         self.morph_per_slice = bool(morph_per_slice)
         self.regions = bool(regions)
+        self.components = CS.components_option(components)       # 0: off, else max_components
         if self.morph_per_slice and self.opening is None and self.closing is None:
             raise ValueError("VolumeSegmenter: morph_per_slice needs opening or closing")
         self._graphed_eval = graphed if isinstance(graphed, GraphedEval) else None
@@ -410,8 +425,28 @@ class VolumeSegmenter:
                 "truth": RG.derive(rows_i[1], rows_f[1], spacing) if labels is not None else None,
                 "figures": RG.region_figures(rows_i, rows_f, spacing) if labels is not None else None}
 
+    def _components(self, final, labels, image, K, components_out, spacing=None):
+        """the component tables and head words of the final mask (0) and of the labels (1), per foreground class, each with the other
+        volume as its `other` and with the query image"""
+        if components_out is not None:
+            rows, heads = components_out
+        else:
+            rows = torch.zeros((2, K - 1, self.components, CS.COMP_ROW), device=final.device, dtype=torch.int64)
+            heads = torch.zeros((2, K - 1, CS.HEAD_WORDS), device=final.device, dtype=torch.int64)
+        for c in range(1, K):
+            CS.component_table(final, cls=c, image=image, other=labels, max_components=self.components, out=rows[0], row=c - 1,
+                               head_out=heads[0, c - 1])
+            if labels is not None:
+                CS.component_table(labels, cls=c, image=image, other=final, max_components=self.components, out=rows[1], row=c - 1,
+                                   head_out=heads[1, c - 1])
+        if components_out is not None:
+            return None
+        rows, heads = rows.cpu().numpy(), heads.cpu().numpy()
+        return {"rows": rows, "head": heads, "scale_log2": CS.default_scale_log2(image),
+                "figures": CS.detection_figures(rows, heads, spacing) if labels is not None else None}
+
     def __call__(self, support_images, support_fg, query_images, appr_query_labels, query_labels=None, counts_out=None, surface_out=None,
-                 post_out=None, spacing=None, post_stats_out=None, morph_stats_out=None, regions_out=None):
+                 post_out=None, spacing=None, post_stats_out=None, morph_stats_out=None, regions_out=None, components_out=None):
         dev = next(self.net.parameters()).device
         morph = self.opening is not None or self.closing is not None
         chain = bool(self.keep_largest) or self.fill_holes is not None or self.min_component is not None or morph
@@ -471,6 +506,12 @@ class VolumeSegmenter:
             RG.check_regions_out(regions_out, K)
             if any(t.device != dev for t in regions_out):
                 raise ValueError(f"regions_out is on {regions_out[0].device}, the net on {dev}")
+        if components_out is not None:
+            if not self.components:
+                raise ValueError("components_out needs VolumeSegmenter(components=...)")
+            CS.check_components_out(components_out, K, self.components)
+            if any(t.device != dev for t in components_out):
+                raise ValueError(f"components_out is on {components_out[0].device}, the net on {dev}")
         nb = -(-S // B)
         pad = nb * B - S
 
@@ -513,6 +554,8 @@ class VolumeSegmenter:
             post = self._post(mask[:S], labels[:S] if labels is not None else None, K, post_out, spacing, post_stats_out, morph_stats_out) if chain else None
             regions = self._regions(post["mask"] if chain else mask[:S], labels[:S] if labels is not None else None, qi[:S, 0], K, regions_out,
                                     spacing) if self.regions else None
+            components = self._components(post["mask"] if chain else mask[:S], labels[:S] if labels is not None else None,
+                                          qi[:S, 0], K, components_out, spacing) if self.components else None
         if counts is None or counts_out is not None:
             res = VolumeResult(mask[:S], None, None)
         else:
@@ -527,4 +570,6 @@ class VolumeSegmenter:
             res.post = post
         if regions is not None:
             res.regions = regions
+        if components is not None:
+            res.components = components
         return res

@@ -29,6 +29,10 @@ support volume per query, then the reference's "Average performance" block (test
 --regions (needs --device-items): every item line gains ` vol <pred> (<truth>) rvd <x> cdist <x>`, the volume of the final mask (of the
 labels), their relative volume difference and the distance of their centroids, in voxels, under --spacing in ml and mm
 (rpnet_amd.regions), every class line their means.
+--components [N] (needs --device-items): every item line gains ` comp <Cp> (<Ct>) det <detected>/<Ct> fp <n> fpvol <voxels>`, the
+connected components of the final mask (of the labels), the label components the mask overlaps, the mask components that overlap no
+label voxel and their volume, in voxels, under --spacing in mL (rpnet_amd.component_stats; N components per class are tallied, 4096
+without N), every class line their means.
 """
 import argparse
 import os
@@ -290,6 +294,9 @@ def build_parser():
     ap.add_argument("--regions", action="store_true",
                     help="with --device-items: volume, relative volume difference and centroid distance of every final mask against the "
                          "labels (rpnet_amd.regions), in voxels, or in ml and mm under --spacing")
+    ap.add_argument("--components", nargs="?", type=int, const=True, default=None, metavar="N",
+                    help="with --device-items: per-component detection counts of every final mask against the labels "
+                         "(rpnet_amd.component_stats), N components tallied per class (4096 without N)")
     ap.add_argument("--fuse-all-voxels", action="store_true", help="with --fuse staple: the voxels all runs agree on take part in the EM")
     return ap
 
@@ -310,6 +317,8 @@ def main():
         raise SystemExit("--runs needs --device-items")
     if a.regions and not a.device_items:
         raise SystemExit("--regions needs --device-items")
+    if a.components is not None and not a.device_items:
+        raise SystemExit("--components needs --device-items")
     if (a.fuse or a.fuse_all_voxels) and a.runs is None:
         raise SystemExit("--fuse and --fuse-all-voxels need --runs")
     min_component = parse_min_component(a.min_component)
@@ -327,6 +336,8 @@ def main():
         post.update(opening=opening, closing=closing, morph_per_slice=a.morph_slice)
     if a.regions:
         post.update(regions=True)
+    if a.components is not None:
+        post.update(components=a.components)
     loader = None if a.device_items else FewshotRegReader(args.data_dir, args.eval_set_name, config, mode="eval")
     net = model_factory[args.net](pretrained_path=config.get("pretrained_path"),
                                   cfg={"align": True, "backbone": config.get("backbone", "vgg")}, backbone_cfg=config).cuda()
